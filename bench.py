@@ -6,6 +6,12 @@ synthetic Delaunay graph (BASELINE.json config: 50k vertices / 150k edges / 500 
 cost of an iteration is data independent, so successive steps simply keep iterating the resident
 state).  N>1 GPUs: one process per GPU, every rank regularises its own frame (replicas, weak
 scaling, no data-path collective).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline figure.  Everything else
+it can measure (repeated windows, per-launch device time and the roofline, host-inclusive frames,
+side configurations, the C++ facade, the CPU baseline, parity with the oracle, the library's
+partition block at N>1) runs only with --full.  --dump-outputs DIR writes what the timed path
+returned after its last step (x, w1, w2, q) as float32 .npy files.
 """
 import argparse
 import json
@@ -17,6 +23,20 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs stays below 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array the timed path's caller receives.  Above the byte budget every
+    array keeps the same fixed, seeded fraction of its rows, so two runs (or two builds) stay comparable row for row."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = np.random.default_rng(0).choice(len(a), int(len(a) * DUMP_BUDGET_BYTES / total), replace=False)
+            a = a[np.sort(keep)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_baseline(workload, batch_win, iters, budget_s=12.0):
@@ -147,7 +167,7 @@ def live_hbm_traffic(kernel, child_args, budget_s=110.0):
             return None
         d = tempfile.mkdtemp(prefix="flame_pmc_", dir="/tmp")
         cmd = ["rocprofv3", "--kernel-trace", "--pmc"] + list(names) + ["--output-format", "csv", "-d", d, "-o", "p", "--",
-               sys.executable, os.path.abspath(__file__), "--no-cpu", "--no-facade", "--steps", "4", "--warmup", "1"] + child_args
+               sys.executable, os.path.abspath(__file__), "--full", "--no-cpu", "--no-facade", "--steps", "4", "--warmup", "1"] + child_args
         try:
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK",
                                                                     "MASTER_ADDR", "MASTER_PORT", "FLAME_BENCH_FORCE_PARTITION")}
@@ -472,9 +492,13 @@ def main():
     ap.add_argument("--host-plan", action="store_true", help="build the plan with the host builder")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=INT",
                     help="extra library option (flame_hip_graph_set_option), repeatable")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-facade", action="store_true", help="skip the facade frame-latency and frames-axis side measurements")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not measure roofline.traffic by two rocprofv3 PMC child runs (quote the committed profile)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, every side measurement and check (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write x, w1, w2, q of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-facade", action="store_true", help="--full: skip the facade frame-latency and frames-axis side measurements")
+    ap.add_argument("--no-live-traffic", action="store_true", help="--full: do not measure roofline.traffic by two rocprofv3 PMC child runs (quote the committed profile)")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--mode", default="replicas", choices=["replicas", "partition"],
                     help="N>1: independent frames per GPU (default) or ONE graph cut into N "
@@ -634,10 +658,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # the state the last timed step left, before any --full measurement iterates it further
+    if args.dump_outputs:
+        if partition:  # (a collective: every rank gathers the whole graph's solution)
+            x, w1, w2, q = ps.gather_solution()
+        elif rank == 0:
+            x, w1, w2, q = r.download()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"x": x, "w1": w1, "w2": w2, "q": q})
+
     # the contract's figure is the ONE window above; it is short (tens of ms), so the same K-step
     # window is repeated a few times afterwards and the spread reported beside it (rank 0 only)
     repeat_ips = []
-    if world == 1:
+    if world == 1 and args.full:
         for _ in range(5):
             r.sync()
             tr0 = time.perf_counter()
@@ -649,20 +682,21 @@ def main():
 
     # per-launch device time with HIP events on the solve stream (outside the timed region so the
     # event pairs do not perturb it): same launches, one solve at a time
-    ev_ms = []
-    for _ in range(min(args.steps, 10)):
-        r.step(p, iters, sync=True)
-        ms, launches = r.last_solve_ms()
-        ev_ms.append(ms)
-    ev_ms.sort()
-    solve_ms = ev_ms[len(ev_ms) // 2]
-    if solve_ms != solve_ms:  # partition mode: no single-handle event pair; use the wall clock
-        solve_ms, launches = elapsed / args.steps * 1e3, max(1, -(-iters // max(1, r.info("tile_depth") or iters)))
+    if args.full:
+        ev_ms = []
+        for _ in range(min(args.steps, 10)):
+            r.step(p, iters, sync=True)
+            ms, launches = r.last_solve_ms()
+            ev_ms.append(ms)
+        ev_ms.sort()
+        solve_ms = ev_ms[len(ev_ms) // 2]
+        if solve_ms != solve_ms:  # partition mode: no single-handle event pair; use the wall clock
+            solve_ms, launches = elapsed / args.steps * 1e3, max(1, -(-iters // max(1, r.info("tile_depth") or iters)))
 
     # PCIe-inclusive frame rate (never `value`): host graph in -> plan build + H2D -> iterations
     # -> D2H of x and the triangle stage, a fresh handle per frame as a real frame stream would do
     frame_ms = None
-    if not partition and not args.batch:
+    if args.full and not partition and not args.batch:
         ts = []
         import ctypes as C
         rf = GraphRegularizer(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, tris=g.tris,
@@ -681,7 +715,7 @@ def main():
         frame_ms = ts[len(ts) // 2]
 
     part_info = None
-    if partition:  # per-exchange cost, measured apart from the timed region: pack + P2P + unpack
+    if partition and args.full:  # per-exchange cost, measured apart from the timed region: pack + P2P + unpack
         torch.cuda.synchronize(); dist.barrier()
         t0x = time.perf_counter()
         for _ in range(20):
@@ -696,12 +730,7 @@ def main():
     if rank == 0:
         nfr = max(args.batch, 1)
         total_iters = (1 if partition else world) * args.steps * iters * nfr
-        alg_bytes_iter = 84 * g.E + 60 * g.V  # SURVEY.md 8(d)
         path = r.info("path")
-        resident = bool(r.info("persist_used"))
-        iters_per_launch = iters / max(launches, 1)
-        launch_us = solve_ms * 1e3 / max(launches, 1)
-        achieved = alg_bytes_iter * iters_per_launch / (launch_us * 1e-6) / 1e9
         out = {
             "metric": "primal-dual iterations/sec on a %d-vertex / %d-edge Delaunay graph" % (g.V, g.E),
             "value": total_iters / elapsed, "unit": "PD iterations/s",
@@ -718,20 +747,33 @@ def main():
                        # resident launches that gave up and were repeated by launches (whole queues included, r05) while this
                        # handle was measured: normally 0; > 0 means some window paid for a repeat -- the value stays valid
                        "resident_solves_repeated": r.info("persist_recovered") if not partition and not args.batch else None},
-            "repeats": ({"windows": len(repeat_ips), "median": repeat_ips[len(repeat_ips) // 2], "min": repeat_ips[0],
-                         "max": repeat_ips[-1], "unit": "PD iterations/s",
-                         "note": "the same K-step window repeated after the timed one"} if repeat_ips else None),
             "frames_per_s": (1 if partition else world) * args.steps * nfr / elapsed,
             "us_per_iteration": elapsed / (args.steps * iters) * 1e6,
-            "roofline": {"bound": "hbm", "contract_bound": "hbm",
-                         "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
-                         "kernel": ("k_tile_persist" if resident else "k_tile") if path == 2 else "k_dual+k_primal",
-                         "launch_us": launch_us, "iters_per_launch": iters_per_launch,
-                         "alg_bytes_per_iter": alg_bytes_iter,
-                         "note": "global path: achieved / frac = (84E+60V) x iterations per launch / mean launch duration "
-                                 "(HIP events on the solve stream, incl. launch gaps) against the HBM peak (SURVEY 8d)."},
         }
+        if args.batch:
+            out["metric"] = "primal-dual iterations/sec over a batch of %d independent %d-vertex graphs" % (
+                args.batch, frames[0].V)
+            out["config"]["workload"] = "batch of %d feature-grid graphs (640x480, win %d), %d PD iterations each" % (
+                args.batch, args.batch_win, iters)
+    else:
+        out = None
+    if rank == 0 and args.full:
+        alg_bytes_iter = 84 * g.E + 60 * g.V  # SURVEY.md 8(d)
+        resident = bool(r.info("persist_used"))
+        iters_per_launch = iters / max(launches, 1)
+        launch_us = solve_ms * 1e3 / max(launches, 1)
+        achieved = alg_bytes_iter * iters_per_launch / (launch_us * 1e-6) / 1e9
+        out["repeats"] = ({"windows": len(repeat_ips), "median": repeat_ips[len(repeat_ips) // 2], "min": repeat_ips[0],
+                           "max": repeat_ips[-1], "unit": "PD iterations/s",
+                           "note": "the same K-step window repeated after the timed one"} if repeat_ips else None)
+        out["roofline"] = {"bound": "hbm", "contract_bound": "hbm",
+                           "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
+                           "kernel": ("k_tile_persist" if resident else "k_tile") if path == 2 else "k_dual+k_primal",
+                           "launch_us": launch_us, "iters_per_launch": iters_per_launch,
+                           "alg_bytes_per_iter": alg_bytes_iter,
+                           "note": "global path: achieved / frac = (84E+60V) x iterations per launch / mean launch duration "
+                                   "(HIP events on the solve stream, incl. launch gaps) against the HBM peak (SURVEY 8d)."}
         if part_info:
             out["partition_torch_harness"] = part_info
         if frame_ms:
@@ -815,10 +857,6 @@ def main():
                               "(four short child runs under --pmc: FETCH_SIZE, WRITE_SIZE, the LDS set, the VALU / wait set; traffic_source says so); a set "
                               "that did not come is the committed rocprofv3 pass of the same sources (counters_source); profiles/summarize.py --roofline recomputes.")
         if args.batch:
-            out["metric"] = "primal-dual iterations/sec over a batch of %d independent %d-vertex graphs" % (
-                args.batch, frames[0].V)
-            out["config"]["workload"] = "batch of %d feature-grid graphs (640x480, win %d), %d PD iterations each" % (
-                args.batch, args.batch_win, iters)
             out["roofline"]["note"] += " Batch mode: value counts frame-iterations; one isolated tile (one CU) per frame."
         if world == 1 and not args.batch and not args.no_facade:
             out["facade_frame_ms"] = facade_frames()
@@ -837,10 +875,8 @@ def main():
                 out["parity_vs_oracle"] = parity_check(g, iters, local_rank, opts)
             out["speedup_vs_cpu_1thread"] = out["value"] / (1 if partition else world) / cb["value"]
             out["speedup_vs_cpu_best"] = out["value"] / (1 if partition else world) / max(cb["best_value"], cb["value"])
-    else:
-        out = None
     lib_part = None
-    if (world > 1 or force_part) and backend == "nccl" and not args.batch and not args.no_partition and not partition:  # (gloo development runs: ranks share a GPU)
+    if args.full and (world > 1 or force_part) and backend == "nccl" and not args.batch and not args.no_partition and not partition:  # (gloo development runs: ranks share a GPU)
         # the LIBRARY's partition mode beside the replicas line: the unique id travels over the torch
         # store, everything else is flame_hip_comm_* / flame_hip_part_* -- RCCL by the library itself, on its own stream
         from flame_ros_amd import partition as fpart

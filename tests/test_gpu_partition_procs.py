@@ -70,7 +70,7 @@ def test_partitioned_hip_solver_processes(gpu, tmp_path, world, depth, iters):
 def test_bench_runs_with_two_ranks(gpu, mode):
     env = dict(os.environ, FLAME_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps",
            "3", "--warmup", "1", "--workload", "5k", "--mode", mode, "--halo-depth", "8"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -134,7 +134,7 @@ def test_bench_partition_glue_at_world_1(gpu):
     (FLAME_BENCH_FORCE_PARTITION): the line must carry `partition` with RCCL's own rank count and bit-exact variants."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["FLAME_BENCH_FORCE_PARTITION"] = "1"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu", "--no-facade"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-facade"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out/r06_final; mkdir -p $O
 timeout 1500 python -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1; tail -n 4 $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -n 2 $O/smoke.log
-python bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06_final/bench.json').read().strip().splitlines()[-1])

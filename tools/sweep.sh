@@ -1,6 +1,6 @@
 #!/bin/bash
 # dev helper (gpurun): bench variants.  usage: scripts_sweep.sh <workload> "<own list>" "<depth list>"
-run() { timeout 300 python bench.py --no-cpu --steps 5 --warmup 1 "$@" 2>&1 | tail -1 | python -c "
+run() { timeout 300 python bench.py --full --no-cpu --steps 5 --warmup 1 "$@" 2>&1 | tail -1 | python -c "
 import sys,json
 l=sys.stdin.read().strip()
 try:
