@@ -1153,8 +1153,8 @@ __global__ __launch_bounds__(256) void k_vtx_normals(int32_t V, const int32_t* _
 
 // ------------------------------------------------------------------------------------------
 // Row a9: optional graph median / low-pass filter of the vertex idepths (Jacobi pass over the
-// incidence CSR; see oracle/nltgv2_oracle.c nltgv2_graph_filter for the exact rule).  The median
-// is found by rank counting (O(deg^2) compares, no per-thread arrays).
+// incidence CSR; see oracle/nltgv2_oracle.c nltgv2_graph_filter for the exact rule, NaN sorting last).
+// The median is found by rank counting (O(deg^2) compares, no per-thread arrays).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_graph_filter(int32_t V, int32_t kind,
                                                       const int32_t* __restrict__ grow,
@@ -1178,7 +1178,7 @@ __global__ __launch_bounds__(256) void k_graph_filter(int32_t V, int32_t kind,
       int32_t rank = 0;
       for (int32_t j = 0; j < n; ++j) {
         const float xj = val(j);
-        rank += (xj < xi) || (xj == xi && j < i);
+        rank += isnan(xi) ? (!isnan(xj) || j < i) : ((xj < xi) || (xj == xi && j < i));  // NaN last
       }
       if (rank == (n - 1) / 2) med = xi;
     }
@@ -1300,6 +1300,20 @@ __device__ __forceinline__ float edge_fn(float ax, float ay, float bx, float by,
   return fmaf(bx - ax, py - ay, -((by - ay) * (px - ax)));
 }
 
+// A pixel test's edge function: evaluated from the edge's lexicographically smaller end point, so the two
+// triangles of a shared edge see exactly opposite values (watertight; oracle edge_w).
+__device__ __forceinline__ float edge_w(float ax, float ay, float bx, float by, float px, float py) {
+  const bool a_first = ax < bx || (ax == bx && ay < by);
+  return a_first ? edge_fn(ax, ay, bx, by, px, py) : -edge_fn(bx, by, ax, ay, px, py);
+}
+
+// The bounding box along one axis of n pixels: clamped to [-1, n] in float before the conversion to int
+// (a vertex beyond 2^31 px must not reach the conversion; oracle raster_span), then to the image.
+__device__ __forceinline__ void raster_span(float lo, float hi, int n, int& i0, int& i1) {
+  i0 = max((int)ceilf(fminf(fmaxf(lo, -1.0f), (float)n)), 0);
+  i1 = min((int)floorf(fminf(fmaxf(hi, -1.0f), (float)n)), n - 1);
+}
+
 // LPT lanes per triangle: 64 for meshes of large triangles (1.2 k vertices on 640 x 480: ~130 pixels
 // each), 8 for dense ones (a 50 k-vertex mesh has 3-pixel triangles: a wave per triangle kept 9 lanes
 // of 64 busy); with 8, a triangle whose bounding box exceeds 256 pixels (hull slivers) is rasterised by
@@ -1310,9 +1324,9 @@ __device__ __forceinline__ void raster_cover(float2 A, float2 B, float2 Cc, int 
   for (int k = first; k < n; k += step) {
     const int jj = x0 + k % bw, ii = y0 + k / bw;
     const float px = (float)jj, py = (float)ii;
-    const float wa = edge_fn(B.x, B.y, Cc.x, Cc.y, px, py);
-    const float wb = edge_fn(Cc.x, Cc.y, A.x, A.y, px, py);
-    const float wc = edge_fn(A.x, A.y, B.x, B.y, px, py);
+    const float wa = edge_w(B.x, B.y, Cc.x, Cc.y, px, py);
+    const float wb = edge_w(Cc.x, Cc.y, A.x, A.y, px, py);
+    const float wc = edge_w(A.x, A.y, B.x, B.y, px, py);
     const bool in = (wa >= 0.f && wb >= 0.f && wc >= 0.f) || (wa <= 0.f && wb <= 0.f && wc <= 0.f);
     if (in) atomicMin(owner + (size_t)ii * width + jj, t);
   }
@@ -1331,10 +1345,9 @@ __device__ __forceinline__ void raster_owner_body(int bid, int32_t T, int32_t wi
   if (live) {
     A = pos[tris[3 * t]]; B = pos[tris[3 * t + 1]]; Cc = pos[tris[3 * t + 2]];
     const float area = edge_fn(A.x, A.y, B.x, B.y, Cc.x, Cc.y);
-    x0 = (int)ceilf(fminf(A.x, fminf(B.x, Cc.x)));
-    y0 = (int)ceilf(fminf(A.y, fminf(B.y, Cc.y)));
-    int x1 = (int)floorf(fmaxf(A.x, fmaxf(B.x, Cc.x))), y1 = (int)floorf(fmaxf(A.y, fmaxf(B.y, Cc.y)));
-    x0 = max(x0, 0); y0 = max(y0, 0); x1 = min(x1, width - 1); y1 = min(y1, height - 1);
+    int x1, y1;
+    raster_span(fminf(A.x, fminf(B.x, Cc.x)), fmaxf(A.x, fmaxf(B.x, Cc.x)), width, x0, x1);
+    raster_span(fminf(A.y, fminf(B.y, Cc.y)), fmaxf(A.y, fmaxf(B.y, Cc.y)), height, y0, y1);
     bw = x1 - x0 + 1; bh = y1 - y0 + 1;
     live = area != 0.0f && bw > 0 && bh > 0;
   }
@@ -1398,9 +1411,9 @@ __global__ __launch_bounds__(256) void k_raster_fill(int32_t width, int32_t heig
     const int32_t a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
     const float2 Pa = pos[a], Pb = pos[b], Pc = pos[c];
     const float px = (float)jj, py = (float)ii;
-    const float wa = edge_fn(Pb.x, Pb.y, Pc.x, Pc.y, px, py);
-    const float wb = edge_fn(Pc.x, Pc.y, Pa.x, Pa.y, px, py);
-    const float wc = edge_fn(Pa.x, Pa.y, Pb.x, Pb.y, px, py);
+    const float wa = edge_w(Pb.x, Pb.y, Pc.x, Pc.y, px, py);
+    const float wb = edge_w(Pc.x, Pc.y, Pa.x, Pa.y, px, py);
+    const float wc = edge_w(Pa.x, Pa.y, Pb.x, Pb.y, px, py);
     const float num = fmaf(wc, A[c].x, fmaf(wb, A[b].x, wa * A[a].x));
     id = num / ((wa + wb) + wc);
   }
@@ -1538,9 +1551,9 @@ __global__ __launch_bounds__(256) void k_dbg_normals(int32_t W, int32_t H, const
   const int32_t a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
   const float2 Pa = pos[a], Pb = pos[b], Pc = pos[c];
   const float px = (float)jj, py = (float)ii;
-  const float wa = edge_fn(Pb.x, Pb.y, Pc.x, Pc.y, px, py);
-  const float wb = edge_fn(Pc.x, Pc.y, Pa.x, Pa.y, px, py);
-  const float wc = edge_fn(Pa.x, Pa.y, Pb.x, Pb.y, px, py);
+  const float wa = edge_w(Pb.x, Pb.y, Pc.x, Pc.y, px, py);
+  const float wb = edge_w(Pc.x, Pc.y, Pa.x, Pa.y, px, py);
+  const float wc = edge_w(Pa.x, Pa.y, Pb.x, Pb.y, px, py);
   const float s = (wa + wb) + wc;
   const float4 na = vn[a], nb = vn[b], nc = vn[c];
   float nx = fmaf(wc, nc.x, fmaf(wb, nb.x, wa * na.x)) / s;

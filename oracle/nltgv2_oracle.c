@@ -375,7 +375,8 @@ int32_t nltgv2_mesh_faces(int32_t T, const int32_t* tris, const uint8_t* tri_val
  * (i) rasterisation of the mesh (upstream getInverseDepthMap / getFilteredInverseDepthMap,
  * reference src/flame_offline_tum.cc:643, src/flame_nodelet.cc:688; the upstream rasteriser is
  * not in the reference tree, so this is the build's own precise rule): a pixel centre (jj, ii)
- * belongs to the LOWEST-index triangle whose three edge functions have one sign (zero included);
+ * belongs to the LOWEST-index triangle whose three edge functions have one sign (zero included;
+ * each evaluated from the edge's lexicographically smaller end point, edge_w: watertight);
  * its idepth is the barycentric interpolation of the vertex idepths; uncovered pixels are NaN;
  * `filtered` keeps only triangles with tri_valid != 0.  (ii) depth = 1/idepth where idepth is not
  * NaN and > 0, else NaN: reference src/flame_offline_tum.cc:650-661.  (iii) cloud: NaN if depth is
@@ -383,6 +384,25 @@ int32_t nltgv2_mesh_faces(int32_t T, const int32_t* tris, const uint8_t* tri_val
  * src/utils.cc:290-312. ---- */
 static inline float edge_fn(float ax, float ay, float bx, float by, float px, float py) {
   return fmaf(bx - ax, py - ay, -((by - ay) * (px - ax)));
+}
+
+/* The edge function a pixel test uses: that of the line through (ax, ay) and (bx, by), evaluated from
+ * the lexicographically smaller end point (and negated when that is b).  The two triangles of a shared
+ * edge then see exactly opposite values at every pixel centre, so none falls between them (no holes);
+ * edge_fn from each triangle's own first vertex rounds differently and left pixels uncovered. */
+static inline float edge_w(float ax, float ay, float bx, float by, float px, float py) {
+  const int a_first = ax < bx || (ax == bx && ay < by);
+  return a_first ? edge_fn(ax, ay, bx, by, px, py) : -edge_fn(bx, by, ax, ay, px, py);
+}
+
+/* The raster's bounding box along one axis of n pixels: clamped to [-1, n] in float BEFORE the
+ * conversion to int (converting a float beyond the int range is undefined: a triangle with a vertex
+ * ~3e9 px out was dropped), then to the image. */
+static inline void raster_span(float lo, float hi, int32_t n, int32_t* i0, int32_t* i1) {
+  const int32_t a = (int32_t)ceilf(fminf(fmaxf(lo, -1.0f), (float)n));
+  const int32_t b = (int32_t)floorf(fminf(fmaxf(hi, -1.0f), (float)n));
+  *i0 = a < 0 ? 0 : a;
+  *i1 = b > n - 1 ? n - 1 : b;
 }
 
 void nltgv2_idepthmap(int32_t width, int32_t height, int32_t T, const float* pos, const float* x,
@@ -396,18 +416,15 @@ void nltgv2_idepthmap(int32_t width, int32_t height, int32_t T, const float* pos
     const float cx = pos[2 * c], cy = pos[2 * c + 1];
     const float area = edge_fn(ax, ay, bx, by, cx, cy);
     if (!(area != 0.0f)) continue;
-    int32_t x0 = (int32_t)ceilf(fminf(ax, fminf(bx, cx))), x1 = (int32_t)floorf(fmaxf(ax, fmaxf(bx, cx)));
-    int32_t y0 = (int32_t)ceilf(fminf(ay, fminf(by, cy))), y1 = (int32_t)floorf(fmaxf(ay, fmaxf(by, cy)));
-    if (x0 < 0) x0 = 0;
-    if (y0 < 0) y0 = 0;
-    if (x1 > width - 1) x1 = width - 1;
-    if (y1 > height - 1) y1 = height - 1;
+    int32_t x0, x1, y0, y1;
+    raster_span(fminf(ax, fminf(bx, cx)), fmaxf(ax, fmaxf(bx, cx)), width, &x0, &x1);
+    raster_span(fminf(ay, fminf(by, cy)), fmaxf(ay, fmaxf(by, cy)), height, &y0, &y1);
     for (int32_t ii = y0; ii <= y1; ++ii)
       for (int32_t jj = x0; jj <= x1; ++jj) {
         const float px = (float)jj, py = (float)ii;
-        const float wa = edge_fn(bx, by, cx, cy, px, py);
-        const float wb = edge_fn(cx, cy, ax, ay, px, py);
-        const float wc = edge_fn(ax, ay, bx, by, px, py);
+        const float wa = edge_w(bx, by, cx, cy, px, py);
+        const float wb = edge_w(cx, cy, ax, ay, px, py);
+        const float wc = edge_w(ax, ay, bx, by, px, py);
         const int in = (wa >= 0.0f && wb >= 0.0f && wc >= 0.0f) || (wa <= 0.0f && wb <= 0.0f && wc <= 0.0f);
         if (!in) continue;
         const float num = fmaf(wc, x[c], fmaf(wb, x[b], wa * x[a]));
@@ -532,18 +549,15 @@ void nltgv2_debug_image(int32_t kind, int32_t W, int32_t H, float scene_color_sc
       const float cx = pos[2 * cc], cy = pos[2 * cc + 1];
       const float area = edge_fn(ax, ay, bx, by, cx, cy);
       if (!(area != 0.0f)) continue;
-      int32_t x0 = (int32_t)ceilf(fminf(ax, fminf(bx, cx))), x1 = (int32_t)floorf(fmaxf(ax, fmaxf(bx, cx)));
-      int32_t y0 = (int32_t)ceilf(fminf(ay, fminf(by, cy))), y1 = (int32_t)floorf(fmaxf(ay, fmaxf(by, cy)));
-      if (x0 < 0) x0 = 0;
-      if (y0 < 0) y0 = 0;
-      if (x1 > W - 1) x1 = W - 1;
-      if (y1 > H - 1) y1 = H - 1;
+      int32_t x0, x1, y0, y1;
+      raster_span(fminf(ax, fminf(bx, cx)), fmaxf(ax, fmaxf(bx, cx)), W, &x0, &x1);
+      raster_span(fminf(ay, fminf(by, cy)), fmaxf(ay, fmaxf(by, cy)), H, &y0, &y1);
       for (int32_t ii = y0; ii <= y1; ++ii)
         for (int32_t jj = x0; jj <= x1; ++jj) {
           const float px = (float)jj, py = (float)ii;
-          const float wa = edge_fn(bx, by, cx, cy, px, py);
-          const float wb = edge_fn(cx, cy, ax, ay, px, py);
-          const float wc = edge_fn(ax, ay, bx, by, px, py);
+          const float wa = edge_w(bx, by, cx, cy, px, py);
+          const float wb = edge_w(cx, cy, ax, ay, px, py);
+          const float wc = edge_w(ax, ay, bx, by, px, py);
           const int in = (wa >= 0.0f && wb >= 0.0f && wc >= 0.0f) || (wa <= 0.0f && wb <= 0.0f && wc <= 0.0f);
           if (!in) continue;
           const float s = (wa + wb) + wc;
@@ -568,7 +582,11 @@ void nltgv2_debug_image(int32_t kind, int32_t W, int32_t H, float scene_color_sc
  * off).  Upstream's arithmetic is not in the reference tree; this is the build's precise rule,
  * Jacobi style (all vertices read the pre-filter values):
  *   median : x_v <- lower median of {x_v} U {x_u : u adjacent to v}  (element (n-1)/2 of the
- *            ascending order; ties broken by position: self first, then incidence order)
+ *            ascending order; ties broken by position: self first, then incidence order, so -0.0
+ *            and +0.0 keep their positions).  NaN sorts after every number (as a stable
+ *            np.argsort does): with k NaNs among the n values the median is the element
+ *            (n-1)/2 of the numbers followed by the NaNs -- a number while (n-1)/2 < n-k, NaN
+ *            otherwise; never a result that depends on where in the incidence list a NaN sits
  *   lowpass: x_v <- (x_v + sum_u x_u) / (1 + deg v), summed self first then in ascending edge id
  * Afterwards the extrapolated value x_bar is set to the filtered x. ---- */
 void nltgv2_graph_filter(nltgv2_graph* g, const int32_t* row, const int32_t* inc, int32_t kind,
@@ -585,7 +603,7 @@ void nltgv2_graph_filter(nltgv2_graph* g, const int32_t* row, const int32_t* inc
         int32_t rank = 0;
         for (int32_t j = 0; j < n; ++j) {
           const float xj = NB_VAL(j);
-          rank += (xj < xi) || (xj == xi && j < i);
+          rank += isnan(xi) ? (!isnan(xj) || j < i) : ((xj < xi) || (xj == xi && j < i));
         }
         if (rank == (n - 1) / 2) med = xi;
       }
