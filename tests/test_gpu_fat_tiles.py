@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from flame_ros_amd.regularizer import GraphRegularizer, default_params
-from tests.util import assert_bit_equal, graphgen, hooks_env, make_oracle, oracle_params, with_hooks
+from tests.util import assert_bit_equal, decoupled, graphgen, hooks_env, make_oracle, oracle_params, with_hooks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,9 +19,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAT = [(60000, 4, 0), (100000, 3, 0), (135000, 2, 0), (160000, 1, 0), (200000, 2, 1)]
 
 
-@pytest.mark.parametrize("V,depth,slot12", FAT)
-def test_fat_resident_tiles_match_oracle(gpu, V, depth, slot12):
+@pytest.mark.parametrize("V,depth,slot12,dec", [pytest.param(*f, 0, id="%d-%d-%d" % f) for f in FAT] +
+                         [pytest.param(100000, 3, 0, 1, id="100000-3-0-decoupled")])
+def test_fat_resident_tiles_match_oracle(gpu, V, depth, slot12, dec):
     g = graphgen.synthetic(V, seed=V)
+    if dec:  # beta independent of alpha, non-uniform data weights with zeros
+        g = decoupled(g, V)
     iters = 90
     o = make_oracle(g)
     o.solve(oracle_params(), iters)

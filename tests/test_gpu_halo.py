@@ -9,14 +9,17 @@ from flame_ros_amd.regularizer import default_params
 from oracle import COracle
 from oracle.cbind import default_params as oracle_params
 from tests.halo_driver import run_subdomains_one_gpu
-from tests.util import graphgen
+from tests.util import decoupled, graphgen
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("world,depth,iters", [(2, 4, 22), (4, 3, 10)])
-def test_subdomains_on_one_gpu(gpu, world, depth, iters):
+@pytest.mark.parametrize("world,depth,iters,dec", [pytest.param(2, 4, 22, 0, id="2-4-22"), pytest.param(4, 3, 10, 0, id="4-3-10"),
+                                                   pytest.param(3, 5, 17, 1, id="3-5-17-decoupled")])
+def test_subdomains_on_one_gpu(gpu, world, depth, iters, dec):
     g = graphgen.synthetic(6000, seed=21)
+    if dec:  # beta independent of alpha, non-uniform data weights with zeros
+        g = decoupled(g, 21)
     subs, solvers = run_subdomains_one_gpu(g, world, depth, iters)
     o = COracle(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt)
     o.solve(oracle_params(), iters)

@@ -9,14 +9,18 @@ import numpy as np
 import pytest
 
 from flame_ros_amd.regularizer import GraphRegularizer, default_params, default_sync_params
-from tests.util import ROOT, assert_bit_equal, graphgen, hooks_env, make_oracle, oracle_params, with_hooks
+from tests.util import ROOT, assert_bit_equal, decoupled, graphgen, hooks_env, make_oracle, oracle_params, with_hooks
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("V", [700, 1000, 1200, 1280])
+@pytest.mark.parametrize("V", [700, 1000, 1200, 1280, "1200:decoupled"])
 def test_one_xcd_graphs_match_the_oracle(gpu, V):
+    dec = V == "1200:decoupled"
+    V = 1200 if dec else V
     g = graphgen.dataset_shaped(640, 480, 16) if V == 1200 else graphgen.synthetic(V, seed=V)
+    if dec:  # beta independent of alpha, non-uniform data weights with zeros
+        g = decoupled(g, V)
     p = default_params()
     o = make_oracle(g)
     with GraphRegularizer(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, tris=g.tris, device=0) as r:

@@ -10,7 +10,7 @@ import pytest
 
 from flame_ros_amd.regularizer import GraphRegularizer, default_params, default_tri_params
 from oracle.cbind import depthmaps as oracle_depthmaps, mesh as oracle_mesh, triangles as oracle_triangles, TriParams as OTri
-from tests.util import assert_bit_equal, graphgen, make_oracle, oracle_params, random_state
+from tests.util import assert_bit_equal, decoupled, graphgen, make_oracle, oracle_params, random_state
 
 pytestmark = pytest.mark.gpu
 
@@ -53,9 +53,12 @@ def compare_state(o, r, what):
 
 
 @pytest.mark.parametrize("path", list(PATHS))
-@pytest.mark.parametrize("V,iters", [(1200, 50), (5000, 200)])
-def test_solve_matches_oracle(gpu, path, V, iters):
+@pytest.mark.parametrize("V,iters,dec", [pytest.param(1200, 50, 0, id="1200-50"), pytest.param(5000, 200, 0, id="5000-200"),
+                                         pytest.param(3000, 120, 1, id="3000-120-decoupled")])
+def test_solve_matches_oracle(gpu, path, V, iters, dec):
     g = graphgen.synthetic(V, seed=1)
+    if dec:  # beta independent of alpha, non-uniform data weights with zeros
+        g = decoupled(g, V)
     o, r = run_both(g, PATHS[path], iters)
     compare_state(o, r, "%s V=%d" % (path, V))
     if path.startswith("tile"):
@@ -153,7 +156,8 @@ def test_batch_of_frames(gpu):
     """Frames axis: a batch of independent feature graphs in one handle (one LDS tile = one
     workgroup per frame, every iteration in a single launch); each frame equals its own oracle."""
     gs = [graphgen.dataset_shaped(640, 480, 16, seed=s) for s in range(6)] + \
-         [graphgen.synthetic(300, seed=9), graphgen.dataset_shaped(320, 240, 8, seed=4)]
+         [graphgen.synthetic(300, seed=9), graphgen.dataset_shaped(320, 240, 8, seed=4),
+          decoupled(graphgen.dataset_shaped(640, 480, 16, seed=6), 6)]
     r = GraphRegularizer.from_batch(gs)
     assert r.info("num_tiles") == len(gs) and r.info("tile_depth") == 0
     r.step(default_params(), 150)
@@ -365,11 +369,13 @@ def test_fuzz_sizes_and_tile_options(gpu):
     counts that are not multiples of 8 for the XCD-aware block map, tiles with very few own
     vertices, and more tiles than the halo can separate): always the oracle's bits."""
     rng = np.random.default_rng(2026)
-    for trial in range(24):
+    for trial in range(28):
         V = int(rng.integers(3, 2500))
         g = graphgen.synthetic(V, seed=100 + trial) if V >= 4 else None
         if g is None:
             continue
+        if trial >= 24:  # the last trials: beta independent of alpha, non-uniform data weights with zeros
+            g = decoupled(g, trial)
         own = int(rng.integers(4, max(5, V // 2)))
         depth = int(rng.integers(1, 9))
         opts = dict(path=2, tile_own=own, tile_depth=depth, balance=int(rng.integers(0, 2)),

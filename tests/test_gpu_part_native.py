@@ -21,12 +21,16 @@ from flame_ros_amd import graphgen, partition
 from flame_ros_amd.regularizer import default_params
 from oracle import COracle
 from oracle.cbind import default_params as oparams
+from tests.util import decoupled
 assert partition.rccl_available()
 uid = partition.unique_id()
 total_recovered = 0
 with partition.Communicator(0, 0, 1, uid) as comm:
-    for V, k, depth, iters, pipe in ((6000, 2, 8, 50, 1), (6000, 2, 8, 50, 0), (9000, 3, 4, 23, 1), (50000, 2, 16, 100, 1)):
+    for V, k, depth, iters, pipe, dec in ((6000, 2, 8, 50, 1, 0), (6000, 2, 8, 50, 0, 0), (9000, 3, 4, 23, 1, 0), (50000, 2, 16, 100, 1, 0),
+                                          (7000, 3, 5, 31, 1, 1)):
         g = graphgen.synthetic(V, seed=5)
+        if dec:  # beta independent of alpha, non-uniform data weights with zeros
+            g = decoupled(g, V)
         with partition.Partition(comm, g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, parts_per_rank=k, halo_depth=depth) as ps:
             p = default_params()
             ps.set_option("pipeline", pipe)  # (forced either way; the default is on from 4 parts per rank.  r05: the records of part i travel while part i + 1 iterates; same bits)

@@ -6,15 +6,18 @@ import numpy as np
 import pytest
 
 from flame_ros_amd.regularizer import GraphRegularizer, default_params
-from tests.util import assert_bit_equal, graphgen, hooks_env, make_oracle, oracle_params, with_hooks
+from tests.util import assert_bit_equal, decoupled, graphgen, hooks_env, make_oracle, oracle_params, with_hooks
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("name,own,depth", [("tum", 40, 5), ("tum", 64, 4), ("v2000", 70, 5), ("v800", 30, 8), ("tum", 40, 2),
-                                            ("tum", 16, 8), ("5k", 0, 0), ("5k", 24, 3), ("euroc", 0, 0), ("euroc", 0, 6)])
+                                            ("tum", 16, 8), ("5k", 0, 0), ("5k", 24, 3), ("euroc", 0, 0), ("euroc", 0, 6),
+                                            ("v2000:decoupled", 70, 5)])
 def test_resident_tiles_match_oracle(gpu, name, own, depth):
-    g, _ = graphgen.named(name)
+    g, _ = graphgen.named(name.split(":")[0])
+    if name.endswith(":decoupled"):  # beta independent of alpha, non-uniform data weights with zeros
+        g = decoupled(g, 2000)
     p = default_params()
     kw = {}
     if own: kw["tile_own"] = own

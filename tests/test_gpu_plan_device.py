@@ -9,7 +9,7 @@ import pytest
 
 from flame_ros_amd import lib as _l
 from flame_ros_amd.regularizer import GraphRegularizer, default_params
-from tests.util import assert_bit_equal, graphgen, host_reference_opts, make_oracle, oracle_params
+from tests.util import assert_bit_equal, decoupled, graphgen, host_reference_opts, make_oracle, oracle_params
 
 pytestmark = pytest.mark.gpu
 
@@ -51,12 +51,15 @@ CASES = [
     ("v160000", dict()),    # (fat tiles, 16-byte slots at depth 1 after two deeper attempts did not fit)
     ("v220000", dict()),    # (fat tiles, 12-byte slots at depth 1)
     ("v100000", dict(persist=0)),  # (not resident: two rounds of smaller tiles, as in r04)
+    ("5k:decoupled", dict()),      # (beta independent of alpha, non-uniform data weights with zeros)
 ]
 
 
 @pytest.mark.parametrize("name,opts", CASES)
 def test_device_plan_equals_host_plan(gpu, name, opts):
-    g, _ = graphgen.named(name)
+    g, _ = graphgen.named(name.split(":")[0])
+    if name.endswith(":decoupled"):
+        g = decoupled(g, 5)
     host = GraphRegularizer(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, tris=g.tris, device=-1, **{**host_reference_opts(), **opts})
     dev = GraphRegularizer(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, tris=g.tris, device=0, **opts)
     compare_plans(host, dev, "%s %s" % (name, opts))

@@ -13,8 +13,12 @@ from tests.util import assert_bit_equal, graphgen, hooks_env, oracle_params, set
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("adaptive,rescale,init_pred", [(0, 0, 1), (1, 0, 1), (0, 1, 0), (1, 1, 1)])
-def test_sync_solve_unscale_triangles(gpu, adaptive, rescale, init_pred):
+@pytest.mark.parametrize("adaptive,rescale,init_pred,rule", [pytest.param(0, 0, 1, 0, id="0-0-1"), pytest.param(1, 0, 1, 0, id="1-0-1"),
+                                                             pytest.param(0, 1, 0, 0, id="0-1-0"), pytest.param(1, 1, 1, 0, id="1-1-1"),
+                                                             pytest.param(1, 1, 1, 3, id="1-1-1-rule3")])
+def test_sync_solve_unscale_triangles(gpu, adaptive, rescale, init_pred, rule):
+    """(rule 3, gains 1.5 / 0.25: alpha = 1.5, beta = 0.25 / len -- the host sync, beta independent of alpha)"""
+    ag, bg = (1.5, 0.25) if rule else (0.0, 0.0)
     K = np.array([[525.0, 0, 319.5], [0, 525.0, 239.5], [0, 0, 1]])
     Kinv = np.linalg.inv(K).astype(np.float32)
     tp = default_tri_params(640, 480)
@@ -25,12 +29,13 @@ def test_sync_solve_unscale_triangles(gpu, adaptive, rescale, init_pred):
         # adaptive weights 1/var reach 1e5: keep the data step tau*lambda*w inside the clamp range
         if adaptive:
             var = np.maximum(var, np.float32(2e-3))
-        sp = default_sync_params(adaptive, rescale, init_pred, 0.01)
-        s = oracle_sync(OSync(adaptive, rescale, init_pred, 0.01), g.pos, g.z, var, g.tris, pred)
+        sp = default_sync_params(adaptive, rescale, init_pred, 0.01, rule, ag, bg)
+        s = oracle_sync(OSync(adaptive, rescale, init_pred, 0.01, rule, ag, bg), g.pos, g.z, var, g.tris, pred)
         o = COracle(g.pos, s["edges"], s["alpha"], s["beta"], s["z"], s["wgt"], x0=s["x0"])
         scale = r.sync_features(g.pos, g.z, var, g.tris, sp, prediction=pred)
         assert np.float32(scale) == np.float32(s["scale"])
-        assert r.info("plan_on_device") == 1  # sync + plan both ran on the GPU
+        if rule == 0:
+            assert r.info("plan_on_device") == 1  # sync + plan both ran on the GPU
         assert np.array_equal(r.edges(), s["edges"])
         o.solve(oracle_params(), 150)
         r.step(default_params(), 150)

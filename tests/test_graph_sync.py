@@ -9,6 +9,7 @@ import pytest
 from flame_ros_amd import lib
 from flame_ros_amd.regularizer import GraphRegularizer, default_sync_params, feature_gate, FlameHipError
 from oracle.cbind import SyncParams as OSync, feature_gate as oracle_gate, graph_sync as oracle_sync
+from tests.solver_corpus import check_sync
 from tests.util import assert_bit_equal, graphgen
 
 
@@ -44,6 +45,7 @@ def test_sync_matches_oracle(adaptive, rescale, init_pred):
         assert scale == 1.0
     if not init_pred:
         assert_bit_equal(want["x0"], want["z"], "x0 = z without prediction")
+    check_sync(want, g.pos, g.z, var, g.tris, pred, adaptive, rescale, init_pred, what="oracle vs float64")
     r.close()
 
 
@@ -62,6 +64,7 @@ def test_sync_upstream_recall_switches(rule, ag, bg):
     b = (np.ones_like(inv) if rule in (1, 2) else inv) * np.float32(bg if bg else 1.0)
     assert_bit_equal(want["alpha"], a, "alpha rule")
     assert_bit_equal(want["beta"], b, "beta rule")
+    check_sync(want, g.pos, g.z, var, g.tris, pred, 0, 0, 1, rule, ag, bg, "oracle vs float64")
     # the solver sees them: t_ew / ew of the plan carry (alpha, beta)
     ew = r.plan_array("ew", np.float32).reshape(-1, 4)
     e_i2o = r.plan_array("e_i2o", np.int32)

@@ -2,6 +2,7 @@
 for this path and the solver source is absent (PARITY UNPINNED), so the oracle is
 pinned by the analytic known-answer tests K1-K9 of SURVEY.md 8c, an independent float64 NumPy
 restatement, and the frozen fixtures in tests/golden/ (made by tests/golden/make_golden.py)."""
+import copy
 import os
 
 import numpy as np
@@ -179,15 +180,23 @@ def test_K8_energy_decreases(g5k):
     assert abs(o.x.mean() - g5k.z.mean()) < 2e-3
 
 
-def test_K9_float64_numpy_restatement(g5k):
-    o = orc(g5k)
-    s = NpSolver(g5k.pos, g5k.edges, g5k.alpha, g5k.beta, g5k.z, g5k.wgt)
-    o.solve(default_params(), 200)
-    s.solve(200)
-    assert np.sqrt(np.mean((s.x - o.x) ** 2)) <= 1e-5
-    sc, dc = o.costs(default_params())
-    sn, dn = s.costs()
-    assert abs(sc - sn) < 1e-3 * sn and abs(dc - dn) < 1e-3 * dn
+def test_K9_float64_numpy_restatement(g5k, ggrid):
+    """The 5k graph from rest (beta = alpha, wgt = 1), and the feature-grid graph with beta = alpha x U(0.5, 2) and
+    non-uniform data weights (zeros among them): a beta read as alpha, or a prox without its weight, shows here."""
+    rng = np.random.default_rng(9)
+    dec = copy.copy(ggrid)
+    dec.beta = (ggrid.alpha * rng.uniform(0.5, 2.0, ggrid.E)).astype(np.float32)
+    dec.wgt = rng.uniform(0.25, 4.0, ggrid.V).astype(np.float32)
+    dec.wgt[::17] = 0.0
+    for g in (g5k, dec):
+        o = orc(g)
+        s = NpSolver(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt)
+        o.solve(default_params(), 200)
+        s.solve(200)
+        assert np.sqrt(np.mean((s.x - o.x) ** 2)) <= 1e-5
+        sc, dc = o.costs(default_params())
+        sn, dn = s.costs()
+        assert abs(sc - sn) < 1e-3 * sn and abs(dc - dn) < 1e-3 * dn
 
 
 def test_projection_equals_clamp():

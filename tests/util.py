@@ -27,6 +27,19 @@ def make_oracle(g, x0=None):
     return COracle(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, x0=x0)
 
 
+def decoupled(g, seed=0):
+    """A copy of graph g whose beta is independent of alpha (alpha x U(0.25, 4)) and whose data weights are not uniform
+    (1 / var, var log-uniform in [1e-4, 10]: 0.1 .. 1e4, every 13th weight zero).  graphgen's defaults stay as they are:
+    bench.py's workload and the golden fixtures depend on them."""
+    import copy
+    rng = np.random.default_rng(seed)
+    d = copy.copy(g)
+    d.beta = (np.asarray(g.alpha, np.float32) * rng.uniform(0.25, 4.0, len(g.alpha)).astype(np.float32)).astype(np.float32)
+    d.wgt = (1.0 / 10.0 ** rng.uniform(-4.0, 1.0, len(g.z))).astype(np.float32)
+    d.wgt[::13] = 0.0
+    return d
+
+
 def random_state(g, seed):
     """A generic non-trivial solver state (exercises every term, incl. saturated duals)."""
     rng = np.random.default_rng(seed)
@@ -93,4 +106,4 @@ def settle_lease(max_solves=5000):
     return n
 
 
-__all__ = ["host_reference_opts", "settle_lease", "ROOT", "HOOKS_LIB", "hooks_env", "with_hooks", "graphgen", "oracle_params", "bits", "assert_bit_equal", "make_oracle", "random_state"]
+__all__ = ["host_reference_opts", "settle_lease", "ROOT", "HOOKS_LIB", "hooks_env", "with_hooks", "graphgen", "oracle_params", "bits", "assert_bit_equal", "make_oracle", "random_state", "decoupled"]
