@@ -10,13 +10,14 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libflame_hip.so")
-SOURCES = ["kernels.hip", "plan_dev.hip", "delaunay_dev.hip", "flame_hip.cpp", "plan.cpp", "sync.cpp", "part.cpp"]
-HEADERS = ["common.h", "kernels.h", "plan.h", "plan_dev.h", "delaunay_dev.h", "sync.h", os.path.join("..", "..", "include", "flame_hip.h")]
+SOURCES = ["kernels.hip", "plan_dev.hip", "delaunay_dev.hip", "frontend.hip", "frontend.cpp", "flame_hip.cpp", "plan.cpp", "sync.cpp", "part.cpp"]
+HEADERS = ["common.h", "kernels.h", "plan.h", "plan_dev.h", "delaunay_dev.h", "frontend.h", "sync.h", os.path.join("..", "..", "include", "flame_hip.h")]
 # -amdgpu-kernarg-preload-count: the first 16 dwords of a kernel's arguments arrive in SGPRs at wave
 # launch (gfx950) instead of through a scalar load -- the tile kernel's argument order relies on it.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
          "-Wno-unused-result", "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 FLAGS_FOR = {}  # extra flags per source file (none today)
+OBJECT_FOR = {"frontend.hip": "frontend_kernels.o"}  # (frontend.cpp, the C ABI beside it, owns frontend.o)
 
 
 def hipcc():
@@ -46,7 +47,7 @@ def build(force=False, verbose=False):
         return LIB
     objs = []
     for s in SOURCES:
-        o = os.path.join(CSRC, os.path.splitext(s)[0] + ".o")
+        o = os.path.join(CSRC, OBJECT_FOR.get(s, os.path.splitext(s)[0] + ".o"))
         cmd = [hipcc()] + FLAGS + FLAGS_FOR.get(s, []) + extra + ["-c", os.path.join(CSRC, s), "-o", o]
         if verbose:
             print(" ".join(cmd))

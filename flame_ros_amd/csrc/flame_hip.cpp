@@ -497,7 +497,7 @@ struct flame_hip_graph {
 
 extern "C" {
 
-int flame_hip_version(void) { return 402; }  // (402, r06: halo view, peer transport, local communicator, handle options instead of environment switches)
+int flame_hip_version(void) { return 403; }  // (403: the feature front end, flame_hip_frontend_*; 402, r06: halo view, peer transport, local communicator, handle options instead of environment switches)
 
 const char* flame_hip_strerror(int code) {
   switch (code) {

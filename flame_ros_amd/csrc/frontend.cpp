@@ -1,0 +1,382 @@
+// flame_ros_amd/csrc/frontend.cpp -- C ABI of the feature front end (include/flame_hip.h, flame_hip_frontend_*): owns the
+// pose-frame ring (images on the device, poses on the host in double), the feature slots and the per-frame scratch; a call
+// of flame_hip_frontend_track uploads the image, queues kill -> track + project -> (detect) -> assign + compact on the
+// handle's stream and returns when the emitted features are on the host.  Kernels: frontend.hip.  Reads no environment variable.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/flame_hip.h"
+#include "frontend.h"
+
+using namespace flamehip;
+
+struct flame_hip_frontend {
+  int device = -1;
+  int32_t W = 0, H = 0, max_features = 0, max_poseframes = 0;
+  double fx = 0, fy = 0, cx = 0, cy = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // pose-frame ring (host side)
+  std::vector<uint32_t> pf_id;
+  std::vector<uint8_t> pf_used;
+  std::vector<double> pf_T;  // 12 per slot: T_world_ref, row-major [R|t]
+  int64_t pf_added = 0;
+  // device
+  uint8_t* d_imgs = nullptr;  // max_poseframes + 1 images
+  FePose* d_poses = nullptr;
+  char* d_state = nullptr;    // one arena for everything sized by max_features
+  unsigned long long* d_cell_key = nullptr;
+  int32_t* d_det = nullptr;
+  int32_t cell_cap = 0;
+  int32_t* d_counts = nullptr;
+  FeFrame fr;  // the pointers, filled once
+  // page-locked host staging
+  uint8_t* h_img = nullptr;
+  FePose* h_poses = nullptr;
+  int32_t* h_counts = nullptr;
+  FeOut* h_out = nullptr;
+  // last frame
+  int32_t n_out = 0;
+  int32_t counts[kFeCounts] = {0};
+  double track_us = 0.0, track_device_us = 0.0;
+  bool timed = false;
+};
+
+namespace {
+
+inline int hip_err(hipError_t e) { return e == hipSuccess ? 0 : FLAME_HIP_ERR_HIP - (int)e; }
+#define FE_HIP(x)                      \
+  do {                                 \
+    const hipError_t e_ = (x);         \
+    if (e_ != hipSuccess) return hip_err(e_); \
+  } while (0)
+
+template <class T>
+T* carve(char*& p, size_t n) {
+  T* r = reinterpret_cast<T*>(p);
+  p += (n * sizeof(T) + 255) & ~(size_t)255;
+  return r;
+}
+
+void release(flame_hip_frontend* fe) {
+  if (fe->device >= 0) {
+    (void)hipSetDevice(fe->device);
+    if (fe->stream) (void)hipStreamSynchronize(fe->stream);
+    if (fe->d_imgs) (void)hipFree(fe->d_imgs);
+    if (fe->d_poses) (void)hipFree(fe->d_poses);
+    if (fe->d_state) (void)hipFree(fe->d_state);
+    if (fe->d_cell_key) (void)hipFree(fe->d_cell_key);
+    if (fe->d_det) (void)hipFree(fe->d_det);
+    if (fe->d_counts) (void)hipFree(fe->d_counts);
+    if (fe->h_img) (void)hipHostFree(fe->h_img);
+    if (fe->h_poses) (void)hipHostFree(fe->h_poses);
+    if (fe->h_counts) (void)hipHostFree(fe->h_counts);
+    if (fe->h_out) (void)hipHostFree(fe->h_out);
+    if (fe->ev0) (void)hipEventDestroy(fe->ev0);
+    if (fe->ev1) (void)hipEventDestroy(fe->ev1);
+    if (fe->stream) (void)hipStreamDestroy(fe->stream);
+  }
+  delete fe;
+}
+
+bool finite12(const double* T) {
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(T[k])) return false;
+  return true;
+}
+
+// A = K R, c = K t of T_cur_ref = T_world_cur^-1 T_world_ref, in double, each entry rounded once to float32.
+// (Sums run left to right; tests/frontend_ref.py pose_record() is the same statement.)
+void pose_record(const flame_hip_frontend* fe, const double* Tc, const double* Tr, FePose* out) {
+  double R[9], t[3];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[3 * i + j] = (Tc[0 * 4 + i] * Tr[0 * 4 + j] + Tc[1 * 4 + i] * Tr[1 * 4 + j]) + Tc[2 * 4 + i] * Tr[2 * 4 + j];
+    const double d0 = Tr[3] - Tc[3], d1 = Tr[7] - Tc[7], d2 = Tr[11] - Tc[11];
+    t[i] = (Tc[0 * 4 + i] * d0 + Tc[1 * 4 + i] * d1) + Tc[2 * 4 + i] * d2;
+  }
+  for (int j = 0; j < 3; ++j) {
+    out->A[0 + j] = (float)(fe->fx * R[0 + j] + fe->cx * R[6 + j]);
+    out->A[3 + j] = (float)(fe->fy * R[3 + j] + fe->cy * R[6 + j]);
+    out->A[6 + j] = (float)R[6 + j];
+  }
+  out->c[0] = (float)(fe->fx * t[0] + fe->cx * t[2]);
+  out->c[1] = (float)(fe->fy * t[1] + fe->cy * t[2]);
+  out->c[2] = (float)t[2];
+}
+
+unsigned long long valid_mask(const flame_hip_frontend* fe) {
+  unsigned long long m = 0;
+  for (int p = 0; p < fe->max_poseframes; ++p)
+    if (fe->pf_used[p]) m |= 1ull << p;
+  return m;
+}
+
+int check_params(const flame_hip_frontend_params* p) {
+  const float fl[] = {p->min_grad_mag, p->epipolar_line_var, p->idepth_min, p->idepth_max, p->idepth_init, p->var_init, p->max_match_error};
+  for (float x : fl)
+    if (!std::isfinite(x)) return FLAME_HIP_ERR_NAN;
+  if (p->detection_win_size < 1 || p->win_size < 1 || p->win_size > kFeMaxWin || !(p->win_size & 1) || p->max_dropouts < 0 ||
+      p->min_grad_mag < 0.f || p->min_grad_mag > 255.f || p->epipolar_line_var < 0.f || !(p->idepth_min < p->idepth_max) ||
+      !(p->var_init > 0.f) || p->max_match_error < 0.f || p->max_match_error > 65025.f)
+    return FLAME_HIP_ERR_ARG;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void flame_hip_frontend_default_params(flame_hip_frontend_params* p) {
+  if (!p) return;
+  p->detection_win_size = 16;
+  p->min_grad_mag = 5.0f;
+  p->win_size = 5;
+  p->epipolar_line_var = 4.0f;
+  p->max_dropouts = 5;
+  p->idepth_min = 0.01f;
+  p->idepth_max = 10.0f;
+  p->idepth_init = 0.5f;
+  p->var_init = 0.25f;
+  p->max_match_error = 100.0f;
+}
+
+int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, int32_t H, const float K[9], int32_t max_features,
+                              int32_t max_poseframes) {
+  if (!out) return FLAME_HIP_ERR_ARG;
+  *out = nullptr;
+  if (!K || W < 8 || H < 8 || W > 8192 || H > 8192 || max_features < 1 || max_features > (1 << 22) || max_poseframes < 1 ||
+      max_poseframes > kFeMaxPoseframes || device < 0)
+    return FLAME_HIP_ERR_ARG;
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(K[k])) return FLAME_HIP_ERR_NAN;
+  if (!(K[0] > 0.f) || !(K[4] > 0.f)) return FLAME_HIP_ERR_ARG;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || device >= n || hipSetDevice(device) != hipSuccess) return FLAME_HIP_ERR_NODEVICE;
+  flame_hip_frontend* fe = new (std::nothrow) flame_hip_frontend();
+  if (!fe) return FLAME_HIP_ERR_ALLOC;
+  fe->device = device;
+  fe->W = W; fe->H = H; fe->max_features = max_features; fe->max_poseframes = max_poseframes;
+  fe->fx = K[0]; fe->fy = K[4]; fe->cx = K[2]; fe->cy = K[5];
+  fe->pf_id.assign(max_poseframes, 0);
+  fe->pf_used.assign(max_poseframes, 0);
+  fe->pf_T.assign(12 * (size_t)max_poseframes, 0.0);
+  const size_t npix = (size_t)W * H, F = (size_t)max_features;
+  const size_t state_bytes = 12 * ((F * 4 + 255) & ~(size_t)255) + ((F + 255) & ~(size_t)255) + ((F * sizeof(float4) + 255) & ~(size_t)255) +
+                             ((F * sizeof(FeOut) + 255) & ~(size_t)255);
+  bool ok = hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&fe->ev0) == hipSuccess &&
+            hipEventCreate(&fe->ev1) == hipSuccess;
+  ok = ok && hipMalloc(&fe->d_imgs, npix * (size_t)(max_poseframes + 1)) == hipSuccess &&
+       hipMalloc(&fe->d_poses, sizeof(FePose) * (size_t)max_poseframes) == hipSuccess && hipMalloc(&fe->d_state, state_bytes) == hipSuccess &&
+       hipMalloc(&fe->d_counts, sizeof(int32_t) * kFeCounts) == hipSuccess &&
+       hipHostMalloc(&fe->h_img, npix) == hipSuccess && hipHostMalloc(&fe->h_poses, sizeof(FePose) * (size_t)max_poseframes) == hipSuccess &&
+       hipHostMalloc(&fe->h_counts, sizeof(int32_t) * kFeCounts) == hipSuccess && hipHostMalloc(&fe->h_out, sizeof(FeOut) * F) == hipSuccess;
+  ok = ok && hipMemsetAsync(fe->d_state, 0, state_bytes, fe->stream) == hipSuccess &&
+       hipMemsetAsync(fe->d_poses, 0, sizeof(FePose) * (size_t)max_poseframes, fe->stream) == hipSuccess &&
+       hipStreamSynchronize(fe->stream) == hipSuccess;
+  if (!ok) {
+    release(fe);
+    return FLAME_HIP_ERR_ALLOC;
+  }
+  FeFrame& f = fe->fr;
+  std::memset(&f, 0, sizeof(f));
+  char* p = fe->d_state;
+  f.u = carve<int32_t>(p, F); f.v = carve<int32_t>(p, F); f.pf = carve<int32_t>(p, F); f.drop = carve<int32_t>(p, F);
+  f.mu = carve<float>(p, F); f.var = carve<float>(p, F);
+  f.status = carve<int32_t>(p, F); f.kstar = carve<int32_t>(p, F); f.cell_of = carve<int32_t>(p, F); f.freelist = carve<int32_t>(p, F);
+  f.alive = carve<uint8_t>(p, F);
+  f.proj = carve<float4>(p, F);
+  f.out = carve<FeOut>(p, F);
+  f.W = W; f.H = H; f.max_features = max_features;
+  f.fx = K[0]; f.fy = K[4]; f.cx = K[2]; f.cy = K[5];
+  f.imgs = fe->d_imgs;
+  f.poses = fe->d_poses;
+  f.counts = fe->d_counts;
+  *out = fe;
+  return 0;
+}
+
+void flame_hip_frontend_destroy(flame_hip_frontend* fe) {
+  if (fe) release(fe);
+}
+
+int flame_hip_frontend_track(flame_hip_frontend* fe, const flame_hip_frontend_params* params, const uint8_t* img, int32_t pitch,
+                             uint32_t img_id, const double T_world_cam[12], int32_t is_poseframe, int32_t* n_out) {
+  if (!fe || !params || !img || !T_world_cam || !n_out || pitch < fe->W) return FLAME_HIP_ERR_ARG;
+  *n_out = 0;
+  if (const int rc = check_params(params)) return rc;
+  if (!finite12(T_world_cam)) return FLAME_HIP_ERR_NAN;
+  const auto t0 = std::chrono::steady_clock::now();
+  FE_HIP(hipSetDevice(fe->device));
+  const int32_t W = fe->W, H = fe->H;
+  const size_t npix = (size_t)W * H;
+  FeFrame& f = fe->fr;
+  f.win = params->win_size;
+  f.dws = params->detection_win_size;
+  f.ncx = (W + f.dws - 1) / f.dws;
+  f.ncy = (H + f.dws - 1) / f.dws;
+  f.max_dropouts = params->max_dropouts;
+  {
+    const double g = std::ceil(4.0 * (double)params->min_grad_mag * (double)params->min_grad_mag);
+    f.g2_min = g < 1.0 ? 1 : (int32_t)g;
+  }
+  f.idepth_min = params->idepth_min; f.idepth_max = params->idepth_max;
+  f.idepth_init = params->idepth_init; f.var_init = params->var_init;
+  f.epipolar_line_var = params->epipolar_line_var;
+  f.bad_match_cost = (uint64_t)((double)params->max_match_error * (double)(f.win * f.win) * 65536.0);
+  f.is_poseframe = is_poseframe ? 1 : 0;
+  const int32_t ncells = f.ncx * f.ncy;
+  if (ncells > fe->cell_cap) {  // (grows with the smallest cell size seen; bounded by the image)
+    FE_HIP(hipStreamSynchronize(fe->stream));
+    if (fe->d_cell_key) (void)hipFree(fe->d_cell_key);
+    if (fe->d_det) (void)hipFree(fe->d_det);
+    fe->d_cell_key = nullptr; fe->d_det = nullptr; fe->cell_cap = 0;
+    FE_HIP(hipMalloc(&fe->d_cell_key, sizeof(unsigned long long) * (size_t)ncells));
+    FE_HIP(hipMalloc(&fe->d_det, sizeof(int32_t) * (size_t)ncells));
+    fe->cell_cap = ncells;
+    f.cell_key = fe->d_cell_key;
+    f.det = fe->d_det;
+  }
+  // a pose frame takes the ring's next slot; the features of the pose frame it overwrites die before tracking
+  int32_t cur = fe->max_poseframes;  // the extra image slot
+  bool overwrote = false;
+  if (is_poseframe) {
+    cur = (int32_t)(fe->pf_added % fe->max_poseframes);
+    overwrote = fe->pf_used[cur] != 0;
+    fe->pf_used[cur] = 0;
+  }
+  f.cur_pf = cur;
+  f.cur = fe->d_imgs + (size_t)cur * npix;
+  for (int p = 0; p < fe->max_poseframes; ++p) {
+    if (fe->pf_used[p]) pose_record(fe, T_world_cam, &fe->pf_T[12 * (size_t)p], &fe->h_poses[p]);
+    else std::memset(&fe->h_poses[p], 0, sizeof(FePose));
+  }
+  for (int32_t y = 0; y < H; ++y) std::memcpy(fe->h_img + (size_t)y * W, img + (size_t)y * pitch, (size_t)W);
+
+  hipStream_t s = fe->stream;
+  FE_HIP(hipEventRecord(fe->ev0, s));
+  FE_HIP(hipMemcpyAsync(fe->d_imgs + (size_t)cur * npix, fe->h_img, npix, hipMemcpyHostToDevice, s));
+  FE_HIP(hipMemcpyAsync(fe->d_poses, fe->h_poses, sizeof(FePose) * (size_t)fe->max_poseframes, hipMemcpyHostToDevice, s));
+  FE_HIP(hipMemsetAsync(fe->d_cell_key, 0xFF, sizeof(unsigned long long) * (size_t)ncells, s));
+  FE_HIP(hipMemsetAsync(fe->d_counts, 0, sizeof(int32_t) * kFeCounts, s));
+  if (overwrote) fe_launch_kill(s, f, valid_mask(fe));
+  fe_launch_track(s, f);
+  if (is_poseframe) fe_launch_detect(s, f);
+  fe_launch_compact(s, f);
+  FE_HIP(hipGetLastError());
+  FE_HIP(hipMemcpyAsync(fe->h_counts, fe->d_counts, sizeof(int32_t) * kFeCounts, hipMemcpyDeviceToHost, s));
+  FE_HIP(hipEventRecord(fe->ev1, s));
+  FE_HIP(hipStreamSynchronize(s));
+  std::memcpy(fe->counts, fe->h_counts, sizeof(fe->counts));
+  fe->n_out = fe->counts[0];
+  if (fe->n_out < 0 || fe->n_out > fe->max_features) return FLAME_HIP_ERR_STATE;
+  if (fe->n_out > 0) {
+    FE_HIP(hipMemcpyAsync(fe->h_out, f.out, sizeof(FeOut) * (size_t)fe->n_out, hipMemcpyDeviceToHost, s));
+    FE_HIP(hipStreamSynchronize(s));
+  }
+  if (is_poseframe) {  // the ring slot is valid from now on
+    fe->pf_used[cur] = 1;
+    fe->pf_id[cur] = img_id;
+    std::memcpy(&fe->pf_T[12 * (size_t)cur], T_world_cam, 12 * sizeof(double));
+    ++fe->pf_added;
+  }
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, fe->ev0, fe->ev1) == hipSuccess) fe->track_device_us = 1000.0 * ms;
+  fe->track_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  *n_out = fe->n_out;
+  return 0;
+}
+
+int flame_hip_frontend_features(flame_hip_frontend* fe, int32_t cap, float* vtx, float* idepth_mu, float* idepth_var, int32_t* slot,
+                                int32_t* status) {
+  if (!fe || cap < fe->n_out) return FLAME_HIP_ERR_ARG;
+  for (int32_t i = 0; i < fe->n_out; ++i) {
+    const FeOut& o = fe->h_out[i];
+    if (vtx) { vtx[2 * i] = o.x; vtx[2 * i + 1] = o.y; }
+    if (idepth_mu) idepth_mu[i] = o.mu;
+    if (idepth_var) idepth_var[i] = o.var;
+    if (slot) slot[i] = o.slot;
+    if (status) status[i] = o.status;
+  }
+  return 0;
+}
+
+int flame_hip_frontend_set_poses(flame_hip_frontend* fe, int32_t n, const uint32_t* ids, const double* T) {
+  if (!fe || n < 0 || (n > 0 && (!ids || !T))) return FLAME_HIP_ERR_ARG;
+  for (int32_t i = 0; i < n; ++i)
+    if (!finite12(T + 12 * (size_t)i)) return FLAME_HIP_ERR_NAN;
+  for (int32_t i = 0; i < n; ++i)
+    for (int p = 0; p < fe->max_poseframes; ++p)
+      if (fe->pf_used[p] && fe->pf_id[p] == ids[i]) std::memcpy(&fe->pf_T[12 * (size_t)p], T + 12 * (size_t)i, 12 * sizeof(double));
+  return 0;  // (an id the ring no longer holds is ignored: the caller's window may be longer than the ring)
+}
+
+int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* keep_ids) {
+  if (!fe || n < 0 || (n > 0 && !keep_ids)) return FLAME_HIP_ERR_ARG;
+  bool dropped = false;
+  for (int p = 0; p < fe->max_poseframes; ++p) {
+    if (!fe->pf_used[p]) continue;
+    bool keep = false;
+    for (int32_t i = 0; i < n; ++i) keep = keep || keep_ids[i] == fe->pf_id[p];
+    if (!keep) { fe->pf_used[p] = 0; dropped = true; }
+  }
+  if (dropped) {
+    FE_HIP(hipSetDevice(fe->device));
+    fe_launch_kill(fe->stream, fe->fr, valid_mask(fe));
+    FE_HIP(hipGetLastError());
+    FE_HIP(hipStreamSynchronize(fe->stream));
+  }
+  return 0;
+}
+
+int flame_hip_frontend_state(flame_hip_frontend* fe, uint8_t* alive, int32_t* u, int32_t* v, int32_t* poseframe, float* mu, float* var,
+                             int32_t* dropouts, int32_t* status, int32_t* kstar) {
+  if (!fe) return FLAME_HIP_ERR_ARG;
+  FE_HIP(hipSetDevice(fe->device));
+  FE_HIP(hipStreamSynchronize(fe->stream));
+  const size_t F = (size_t)fe->max_features;
+  const FeFrame& f = fe->fr;
+  if (alive) FE_HIP(hipMemcpy(alive, f.alive, F, hipMemcpyDeviceToHost));
+  if (u) FE_HIP(hipMemcpy(u, f.u, 4 * F, hipMemcpyDeviceToHost));
+  if (v) FE_HIP(hipMemcpy(v, f.v, 4 * F, hipMemcpyDeviceToHost));
+  if (poseframe) FE_HIP(hipMemcpy(poseframe, f.pf, 4 * F, hipMemcpyDeviceToHost));
+  if (mu) FE_HIP(hipMemcpy(mu, f.mu, 4 * F, hipMemcpyDeviceToHost));
+  if (var) FE_HIP(hipMemcpy(var, f.var, 4 * F, hipMemcpyDeviceToHost));
+  if (dropouts) FE_HIP(hipMemcpy(dropouts, f.drop, 4 * F, hipMemcpyDeviceToHost));
+  if (status) FE_HIP(hipMemcpy(status, f.status, 4 * F, hipMemcpyDeviceToHost));
+  if (kstar) FE_HIP(hipMemcpy(kstar, f.kstar, 4 * F, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value) {
+  if (!fe || !key || !value) return FLAME_HIP_ERR_ARG;
+  static const char* const kStatus[] = {"ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died"};
+  for (int k = 0; k < 7; ++k)
+    if (!std::strcmp(key, kStatus[k])) { *value = fe->counts[2 + k]; return 0; }
+  if (!std::strcmp(key, "emitted")) { *value = fe->n_out; return 0; }
+  if (!std::strcmp(key, "detections_dropped")) { *value = fe->counts[9]; return 0; }
+  if (!std::strcmp(key, "track_us")) { *value = (int64_t)(fe->track_us + 0.5); return 0; }
+  if (!std::strcmp(key, "track_device_us")) { *value = (int64_t)(fe->track_device_us + 0.5); return 0; }
+  if (!std::strcmp(key, "max_features")) { *value = fe->max_features; return 0; }
+  if (!std::strcmp(key, "poseframes")) {
+    int64_t c = 0;
+    for (int p = 0; p < fe->max_poseframes; ++p) c += fe->pf_used[p] ? 1 : 0;
+    *value = c;
+    return 0;
+  }
+  if (!std::strcmp(key, "live")) {  // counted where the state lives (a prune since the last frame shows)
+    std::vector<uint8_t> a((size_t)fe->max_features);
+    if (const int rc = flame_hip_frontend_state(fe, a.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+    int64_t c = 0;
+    for (uint8_t x : a) c += x ? 1 : 0;
+    *value = c;
+    return 0;
+  }
+  return FLAME_HIP_ERR_ARG;
+}
+
+}  // extern "C"

@@ -1,0 +1,66 @@
+// flame_ros_amd/csrc/frontend.h -- the feature front end on the GPU: gradient-maximum detection on a cell grid and epipolar
+// inverse-depth tracking (the first two stages of upstream's Flame::update()).  Kernels: frontend.hip; C ABI:
+// frontend.cpp (include/flame_hip.h, flame_hip_frontend_*); the algorithm statement: DESIGN.md "Feature front end".
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace flamehip {
+
+constexpr int kFeMaxSamples = 256;    // S <= 256 steps, i.e. up to 257 samples of a search = 5 passes of the 64 lanes
+constexpr int kFePasses = 5;
+constexpr int kFeMaxPoseframes = 64;  // the ring's valid slots travel as one 64-bit mask
+constexpr int kFeMaxWin = 9;
+
+// per-slot status of the last frame (FLAME_HIP_FE_* of include/flame_hip.h)
+enum { kFeOk = 0, kFeNoParallax = 1, kFeOutside = 2, kFeBadMatch = 3, kFeAmbiguous = 4, kFeNew = 5, kFeDied = 6, kFeFree = -1 };
+constexpr int kFeCounts = 16;  // counts[]: 0 = emitted, 1 = live, 2 + status = features of that status, 9 = detections dropped (no free slot)
+
+// A = K R and c = K t of T_cur_ref, rounded once to float32 on the host (one record per pose-frame ring slot)
+struct FePose {
+  float A[9];
+  float c[3];
+};
+
+// one emitted feature (the frame's output record, compacted in ascending slot order)
+struct FeOut {
+  float x, y, mu, var;
+  int32_t slot, status;
+};
+
+struct FeFrame {
+  // geometry and parameters of this call
+  int32_t W, H, max_features, win, dws, ncx, ncy, max_dropouts, g2_min, is_poseframe, cur_pf;
+  float fx, fy, cx, cy, idepth_min, idepth_max, idepth_init, var_init, epipolar_line_var;
+  uint64_t bad_match_cost;
+  // images: ring slot p at imgs + p * W * H (dense rows); the current image is one of them or the extra slot
+  const uint8_t* imgs;
+  const uint8_t* cur;
+  const FePose* poses;
+  // feature state, one entry per slot
+  uint8_t* alive;
+  int32_t* u;
+  int32_t* v;
+  int32_t* pf;
+  int32_t* drop;
+  float* mu;
+  float* var;
+  // per-frame results per slot
+  int32_t* status;
+  int32_t* kstar;
+  int32_t* cell_of;  // detection cell of the projected feature, -1 = not a candidate for emission
+  float4* proj;      // {x, y, idepth, var} in the current frame
+  // per-frame grids and lists
+  unsigned long long* cell_key;  // per cell: min over candidates of (bits(var_cur) << 32 | slot); all ones = empty
+  int32_t* det;                  // per cell: y << 16 | x of the detection, -1 = none
+  int32_t* freelist;             // max_features
+  FeOut* out;                    // max_features
+  int32_t* counts;               // kFeCounts
+};
+
+void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask);
+void fe_launch_track(hipStream_t s, const FeFrame& f);
+void fe_launch_detect(hipStream_t s, const FeFrame& f);
+void fe_launch_compact(hipStream_t s, const FeFrame& f);
+
+}  // namespace flamehip

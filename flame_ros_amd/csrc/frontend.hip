@@ -1,0 +1,387 @@
+// flame_ros_amd/csrc/frontend.hip -- kernels of the feature front end (gfx950): epipolar inverse-depth tracking, one wavefront
+// per live feature with the lanes over the samples of its search (k_fe_track); gradient-maximum detection, one wavefront per
+// grid cell (k_fe_detect); slot assignment of the detections and compaction of the emitted features (k_fe_compact).
+//
+// Arithmetic contract (DESIGN.md "Feature front end"): float32 with + - x / sqrtf floorf ceilf only, every operation rounded
+// on its own (-ffp-contract=off, NO fmaf here: the restatement in tests/frontend_ref.py is NumPy, which has none), image costs
+// are integers -- any reduction order gives the same bits.  The statement is this build's own ([UPSTREAM-RECALL] where it
+// follows the paper); tests/frontend_ref.py restates it operation by operation and the GPU must equal it bit for bit.
+//
+// Memory: images are dense (row pitch = W) uint8, rows start at any byte address -- every pixel load is a byte load (a 640x480
+// image stays in L2; no alignment is assumed).  No LDS in the tracker: a lane keeps the costs of its (up to 5) samples in
+// registers, the winner's neighbours travel by lane shuffles.
+#include "frontend.h"
+
+namespace flamehip {
+
+namespace {
+
+constexpr unsigned long long kNone = ~0ull;
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(v, o, 64);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+__device__ __forceinline__ bool fe_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }
+
+// Cost of one sample: sum over the win x win window of (bilinear(cur, p) * 256 - 256 * ref)^2 with p quantised to 1/16 px;
+// kNone when the window (with its +1 bilinear neighbours) leaves the image.  Per row two running pixels are carried, so a
+// window pixel costs two loads of the current image and one of the reference patch.
+__device__ __forceinline__ unsigned long long fe_cost(const FeFrame& f, const uint8_t* __restrict__ ref, int u, int v, float px,
+                                                      float py) {
+  const float fqx = floorf(px * 16.0f + 0.5f), fqy = floorf(py * 16.0f + 0.5f);
+  if (!(fqx >= 0.0f && fqx <= (float)(16 * f.W) && fqy >= 0.0f && fqy <= (float)(16 * f.H))) return kNone;
+  const int qx = (int)fqx, qy = (int)fqy;
+  const int ix = qx >> 4, iy = qy >> 4;
+  const int r = f.win >> 1;
+  if (ix - r < 0 || iy - r < 0 || ix + r + 1 > f.W - 1 || iy + r + 1 > f.H - 1) return kNone;
+  const int wx1 = qx & 15, wx0 = 16 - wx1, wy1 = qy & 15, wy0 = 16 - wy1;
+  unsigned long long C = 0;
+  for (int dy = -r; dy <= r; ++dy) {
+    const uint8_t* __restrict__ r0 = f.cur + (size_t)(iy + dy) * f.W + (ix - r);
+    const uint8_t* __restrict__ r1 = r0 + f.W;
+    const uint8_t* __restrict__ rr = ref + (size_t)(v + dy) * f.W + (u - r);
+    int t0 = r0[0], b0 = r1[0];
+    for (int dx = 0; dx < f.win; ++dx) {
+      const int t1 = r0[dx + 1], b1 = r1[dx + 1];
+      const int D = wy0 * (wx0 * t0 + wx1 * t1) + wy1 * (wx0 * b0 + wx1 * b1) - 256 * (int)rr[dx];
+      const unsigned int aD = (unsigned int)(D < 0 ? -D : D);  // <= 65 280: the square fits 32 bits
+      C += (unsigned long long)(aD * aD);
+      t0 = t1;
+      b0 = b1;
+    }
+  }
+  return C;
+}
+
+__global__ __launch_bounds__(256) void k_fe_kill(FeFrame f, unsigned long long valid_mask) {
+  const int slot = blockIdx.x * 256 + threadIdx.x;
+  if (slot >= f.max_features) return;
+  if (f.alive[slot] && !((valid_mask >> f.pf[slot]) & 1ull)) f.alive[slot] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
+  const int lane = threadIdx.x & 63;
+  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= f.max_features) return;  // (whole wavefronts leave: everything below is wave-level)
+  if (!f.alive[slot]) {
+    if (lane == 0) {
+      f.status[slot] = kFeFree;
+      f.kstar[slot] = -1;
+      f.cell_of[slot] = -1;
+    }
+    return;
+  }
+  const int u = f.u[slot], v = f.v[slot], p = f.pf[slot];
+  float mu = f.mu[slot], var = f.var[slot];
+  int drop = f.drop[slot];
+  const FePose P = f.poses[p];
+  const uint8_t* __restrict__ ref = f.imgs + (size_t)p * f.W * f.H;
+
+  const float b0 = ((float)u - f.cx) / f.fx, b1 = ((float)v - f.cy) / f.fy;
+  const float a0 = (P.A[0] * b0 + P.A[1] * b1) + P.A[2];
+  const float a1 = (P.A[3] * b0 + P.A[4] * b1) + P.A[5];
+  const float a2 = (P.A[6] * b0 + P.A[7] * b1) + P.A[8];
+  const float c0 = P.c[0], c1 = P.c[1], c2 = P.c[2];
+  const float two = 2.0f * sqrtf(var);
+  const float lo = mu - two, hi = mu + two;
+  const float xi0 = lo > f.idepth_min ? lo : f.idepth_min;
+  const float xi1 = hi < f.idepth_max ? hi : f.idepth_max;
+  const float d0 = a2 + xi0 * c2, d1 = a2 + xi1 * c2;
+  const int r = f.win >> 1;
+  const bool ref_in = u - r >= 0 && v - r >= 0 && u + r <= f.W - 1 && v + r <= f.H - 1;
+
+  int status, ks = -1;
+  float mu_new = mu, var_new = var;
+  if (!(d0 > 0.0f && d1 > 0.0f) || !ref_in) {
+    status = kFeOutside;  // an end of the search lies behind the camera / the reference patch leaves its image
+  } else {
+    const float x0 = (a0 + xi0 * c0) / d0, y0 = (a1 + xi0 * c1) / d0;
+    const float x1 = (a0 + xi1 * c0) / d1, y1 = (a1 + xi1 * c1) / d1;
+    const float dx = x1 - x0, dy = y1 - y0;
+    const float L = sqrtf(dx * dx + dy * dy);
+    if (!(L >= 2.0f)) {
+      status = kFeNoParallax;
+    } else {
+      const int S = L >= (float)kFeMaxSamples ? kFeMaxSamples : (int)ceilf(L);
+      const float ex = dx / (float)S, ey = dy / (float)S;
+      unsigned long long C[kFePasses];
+      unsigned long long best = kNone;
+#pragma unroll
+      for (int pass = 0; pass < kFePasses; ++pass) {
+        const int k = lane + 64 * pass;
+        unsigned long long c = kNone;
+        if (64 * pass <= S && k <= S) c = fe_cost(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey);
+        C[pass] = c;
+        if (c != kNone) {  // (c < 2^39, k < 2^9: one 64-bit key orders by cost, then by k)
+          const unsigned long long key = (c << 9) | (unsigned long long)k;
+          best = key < best ? key : best;
+        }
+      }
+      best = wave_min_u64(best);
+      if (best == kNone) {
+        status = kFeOutside;
+      } else {
+        ks = (int)(best & 511ull);
+        const unsigned long long Cbest = best >> 9;
+        if (Cbest > f.bad_match_cost) {
+          status = kFeBadMatch;
+        } else {
+          bool amb = false;
+#pragma unroll
+          for (int pass = 0; pass < kFePasses; ++pass) {
+            const int k = lane + 64 * pass;
+            const int dk = k > ks ? k - ks : ks - k;
+            if (C[pass] != kNone && dk > 2 && 2ull * C[pass] < 3ull * Cbest) amb = true;
+          }
+          if (__ballot(amb) != 0ull) {
+            status = kFeAmbiguous;
+          } else {
+            // the winner's neighbours: sample k sits in lane k & 63, pass k >> 6 (k > S holds kNone already)
+            unsigned long long Cm = kNone, Cp = kNone;
+            {
+              const int km = ks > 0 ? ks - 1 : 0, kp = ks + 1;
+              unsigned long long sm = C[0], sp = C[0];
+#pragma unroll
+              for (int pass = 1; pass < kFePasses; ++pass) {
+                if ((km >> 6) == pass) sm = C[pass];
+                if ((kp >> 6) == pass) sp = C[pass];
+              }
+              sm = __shfl(sm, km & 63, 64);
+              sp = __shfl(sp, kp & 63, 64);
+              if (ks > 0) Cm = sm;
+              Cp = sp;
+            }
+            float delta = 0.0f;
+            if (Cm != kNone && Cp != kNone) {
+              const float fm = (float)Cm, f0 = (float)Cbest, fp = (float)Cp;
+              const float den = (fm - 2.0f * f0) + fp;
+              if (den > 0.0f) delta = (0.5f * (fm - fp)) / den;
+            }
+            const float t = (float)ks + delta;
+            const float xs = x0 + t * ex, ys = y0 + t * ey;
+            const bool xdom = __builtin_fabsf(ex) >= __builtin_fabsf(ey);
+            float xi_m, xi_p, xi_n;
+            if (xdom) {
+              const float xp = xs + ex, xn = xs - ex;
+              xi_m = (a0 - xs * a2) / (xs * c2 - c0);
+              xi_p = (a0 - xp * a2) / (xp * c2 - c0);
+              xi_n = (a0 - xn * a2) / (xn * c2 - c0);
+            } else {
+              const float yp = ys + ey, yn = ys - ey;
+              xi_m = (a1 - ys * a2) / (ys * c2 - c1);
+              xi_p = (a1 - yp * a2) / (yp * c2 - c1);
+              xi_n = (a1 - yn * a2) / (yn * c2 - c1);
+            }
+            const float s = (xi_p - xi_n) * 0.5f;
+            const float var_m = (s * s) * f.epipolar_line_var;
+            const float den = var + var_m;
+            const float mu_f = (mu * var_m + xi_m * var) / den;
+            const float var_f = (var * var_m) / den;
+            if (fe_finite(xi_m) && fe_finite(var_m) && fe_finite(mu_f) && fe_finite(var_f)) {
+              status = kFeOk;
+              mu_new = mu_f;
+              var_new = var_f;
+            } else {
+              status = kFeBadMatch;  // a degenerate measurement (the search ran along a line of constant inverse depth)
+            }
+          }
+        }
+      }
+    }
+  }
+
+  const bool failed = status == kFeOutside || status == kFeBadMatch || status == kFeAmbiguous;
+  if (status == kFeOk) {
+    mu = mu_new;
+    var = var_new;
+    drop = 0;
+  }
+  // projection into the current frame
+  const float w0 = a0 + mu * c0, w1 = a1 + mu * c1, w2 = a2 + mu * c2;
+  bool pok = false;
+  float px = 0.0f, py = 0.0f, xc = 0.0f, vc = 0.0f;
+  if (w2 > 0.0f) {
+    px = w0 / w2;
+    py = w1 / w2;
+    xc = mu / w2;
+    const float g = a2 / (w2 * w2);
+    vc = var * (g * g);
+    pok = px >= 0.0f && px <= (float)(f.W - 1) && py >= 0.0f && py <= (float)(f.H - 1) && fe_finite(xc) && fe_finite(vc) &&
+          vc >= 0.0f;
+  }
+  if (failed || !pok) drop += 1;
+  const bool dies = drop > f.max_dropouts;
+  if (lane == 0) {
+    f.mu[slot] = mu;
+    f.var[slot] = var;
+    f.drop[slot] = drop;
+    f.kstar[slot] = ks;
+    atomicAdd(&f.counts[2 + status], 1);
+    if (dies) {
+      f.alive[slot] = 0;
+      f.status[slot] = kFeDied;
+      f.cell_of[slot] = -1;
+      atomicAdd(&f.counts[2 + kFeDied], 1);
+    } else {
+      f.status[slot] = status;
+      int cell = -1;
+      if (pok) {
+        cell = ((int)py / f.dws) * f.ncx + (int)px / f.dws;
+        // one emitted feature per cell: smallest variance, then lowest slot
+        atomicMin(&f.cell_key[cell], ((unsigned long long)__float_as_uint(vc) << 32) | (unsigned long long)(unsigned int)slot);
+        f.proj[slot] = make_float4(px, py, xc, vc);
+      }
+      f.cell_of[slot] = cell;
+    }
+  }
+}
+
+// One wavefront per cell: the cell's largest squared central-difference gradient, ties to the smallest y, then the smallest x.
+__global__ __launch_bounds__(256) void k_fe_detect(FeFrame f) {
+  const int lane = threadIdx.x & 63;
+  const int cell = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (cell >= f.ncx * f.ncy) return;
+  if (f.cell_key[cell] != kNone) {  // occupied by an emitted feature of this frame
+    if (lane == 0) f.det[cell] = -1;
+    return;
+  }
+  const int ccx = cell % f.ncx, ccy = cell / f.ncx, m = (f.win >> 1) + 1;
+  const int xlo = max(ccx * f.dws, m), xhi = min(ccx * f.dws + f.dws, f.W - m);
+  const int ylo = max(ccy * f.dws, m), yhi = min(ccy * f.dws + f.dws, f.H - m);
+  const int cw = xhi - xlo, ch = yhi - ylo;
+  unsigned long long best = 0ull;
+  if (cw > 0 && ch > 0) {
+    for (int i = lane; i < cw * ch; i += 64) {
+      const int y = ylo + i / cw, x = xlo + i % cw;
+      const uint8_t* __restrict__ q = f.cur + (size_t)y * f.W + x;
+      const int gx = (int)q[1] - (int)q[-1], gy = (int)q[f.W] - (int)q[-f.W];
+      const unsigned long long key = ((unsigned long long)(unsigned int)(gx * gx + gy * gy) << 32) |
+                                     ((unsigned long long)(0xFFFF - y) << 16) | (unsigned long long)(0xFFFF - x);
+      best = key > best ? key : best;
+    }
+  }
+  best = wave_max_u64(best);
+  if (lane == 0) {
+    const int g2 = (int)(best >> 32);
+    f.det[cell] = g2 >= f.g2_min ? ((0xFFFF - (int)((best >> 16) & 0xFFFFull)) << 16) | (0xFFFF - (int)(best & 0xFFFFull)) : -1;
+  }
+}
+
+// exclusive rank of the set flags over the block's 1024 threads, and their number
+__device__ __forceinline__ int fe_block_rank(bool flag, int* s_w, int* total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const unsigned long long b = __ballot(flag);
+  const int within = __popcll(b & ((1ull << lane) - 1ull));
+  __syncthreads();  // (the previous call's readers are done)
+  if (lane == 0) s_w[wv] = __popcll(b);
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = s_w[i];
+    if (i < wv) base += c;
+    tot += c;
+  }
+  *total = tot;
+  return base + within;
+}
+
+// ONE workgroup: on a pose frame the detections take the free slots (ascending slots, cells in row-major order); then the emitted
+// features -- the winner of every cell -- are compacted in ascending slot order.
+__global__ __launch_bounds__(1024) void k_fe_compact(FeFrame f) {
+  __shared__ int s_w[16];
+  const int tid = threadIdx.x;
+  int n_new = 0, n_dropped = 0;
+  if (f.is_poseframe) {
+    int nfree = 0, ndet = 0, tot = 0;
+    for (int base = 0; base < f.max_features; base += 1024) {
+      const int slot = base + tid;
+      const bool fr = slot < f.max_features && !f.alive[slot];
+      const int rk = fe_block_rank(fr, s_w, &tot);
+      if (fr) f.freelist[nfree + rk] = slot;
+      nfree += tot;
+    }
+    __syncthreads();
+    const int ncells = f.ncx * f.ncy;
+    for (int base = 0; base < ncells; base += 1024) {
+      const int cell = base + tid;
+      const int d = cell < ncells ? f.det[cell] : -1;
+      const int rk = fe_block_rank(d >= 0, s_w, &tot);
+      if (d >= 0 && ndet + rk < nfree) {
+        const int slot = f.freelist[ndet + rk];
+        const int x = d & 0xFFFF, y = d >> 16;
+        f.alive[slot] = 1;
+        f.u[slot] = x;
+        f.v[slot] = y;
+        f.pf[slot] = f.cur_pf;
+        f.drop[slot] = 0;
+        f.mu[slot] = f.idepth_init;
+        f.var[slot] = f.var_init;
+        f.status[slot] = kFeNew;
+        f.kstar[slot] = -1;
+        f.cell_of[slot] = cell;
+        f.proj[slot] = make_float4((float)x, (float)y, f.idepth_init, f.var_init);
+        f.cell_key[cell] = ((unsigned long long)__float_as_uint(f.var_init) << 32) | (unsigned long long)(unsigned int)slot;
+      }
+      ndet += tot;
+    }
+    __syncthreads();
+    n_new = ndet < nfree ? ndet : nfree;
+    n_dropped = ndet - n_new;
+  }
+  int nout = 0, nlive = 0, tot = 0;
+  for (int base = 0; base < f.max_features; base += 1024) {
+    const int slot = base + tid;
+    const bool al = slot < f.max_features && f.alive[slot];
+    const int c = al ? f.cell_of[slot] : -1;
+    const bool emit = c >= 0 && (unsigned int)(f.cell_key[c] & 0xFFFFFFFFull) == (unsigned int)slot;
+    const int rk = fe_block_rank(emit, s_w, &tot);
+    if (emit) {
+      const float4 pr = f.proj[slot];
+      FeOut o;
+      o.x = pr.x; o.y = pr.y; o.mu = pr.z; o.var = pr.w;
+      o.slot = slot;
+      o.status = f.status[slot];
+      f.out[nout + rk] = o;
+    }
+    nout += tot;
+    (void)fe_block_rank(al, s_w, &tot);
+    nlive += tot;
+  }
+  if (tid == 0) {
+    f.counts[0] = nout;
+    f.counts[1] = nlive;
+    f.counts[2 + kFeNew] = n_new;
+    f.counts[9] = n_dropped;
+  }
+}
+
+}  // namespace
+
+void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask) {
+  hipLaunchKernelGGL(k_fe_kill, dim3((f.max_features + 255) / 256), dim3(256), 0, s, f, valid_mask);
+}
+void fe_launch_track(hipStream_t s, const FeFrame& f) {
+  hipLaunchKernelGGL(k_fe_track, dim3((f.max_features + 3) / 4), dim3(256), 0, s, f);
+}
+void fe_launch_detect(hipStream_t s, const FeFrame& f) {
+  hipLaunchKernelGGL(k_fe_detect, dim3((f.ncx * f.ncy + 3) / 4), dim3(256), 0, s, f);
+}
+void fe_launch_compact(hipStream_t s, const FeFrame& f) {
+  hipLaunchKernelGGL(k_fe_compact, dim3(1), dim3(1024), 0, s, f);
+}
+
+}  // namespace flamehip

@@ -1,0 +1,119 @@
+"""Host-side mirror of the feature front end's C ABI (include/flame_hip.h, flame_hip_frontend_*).
+
+`GpuFrontEnd` owns one handle: pose-frame images and feature slots live on the GPU; `track()` takes a grey
+image and a world pose and returns the frame's emitted features.  Everything computes in libflame_hip.so;
+there is no CPU path in this module (the NumPy restatement the tests compare with is tests/frontend_ref.py).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import lib as _l
+from .lib import FlameHipError  # noqa: F401
+
+FE_OK, FE_NO_PARALLAX, FE_OUTSIDE, FE_BAD_MATCH, FE_AMBIGUOUS, FE_NEW, FE_DIED, FE_FREE = 0, 1, 2, 3, 4, 5, 6, -1
+STATUS_KEYS = ("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died")
+
+
+class FrontEndParams(C.Structure):
+    """flame_hip_frontend_params."""
+    _fields_ = [("detection_win_size", C.c_int32), ("min_grad_mag", C.c_float), ("win_size", C.c_int32),
+                ("epipolar_line_var", C.c_float), ("max_dropouts", C.c_int32), ("idepth_min", C.c_float),
+                ("idepth_max", C.c_float), ("idepth_init", C.c_float), ("var_init", C.c_float),
+                ("max_match_error", C.c_float)]
+
+
+def default_frontend_params(**overrides):
+    """The library's defaults (flame::Params' feature fields + the front end's own), with overrides."""
+    p = FrontEndParams()
+    _l.load().flame_hip_frontend_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(FrontEndParams._fields_):
+            raise TypeError("unknown front-end parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _pose(T):
+    T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
+    if T.shape != (12,):
+        raise ValueError("a pose is a row-major 3x4 [R|t]")
+    return T
+
+
+class GpuFrontEnd:
+    """One `flame_hip_frontend` handle."""
+
+    def __init__(self, width, height, K, max_features=2048, max_poseframes=8, device=0):
+        self._lib = _l.load()
+        self._h = C.c_void_p()
+        self.W, self.H, self.max_features = int(width), int(height), int(max_features)
+        K = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        _l.check(self._lib.flame_hip_frontend_create(C.byref(self._h), device, self.W, self.H, _ptr(K), self.max_features,
+                                                     int(max_poseframes)), "flame_hip_frontend_create")
+
+    def close(self):
+        if self._h:
+            self._lib.flame_hip_frontend_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def track(self, params, img, img_id, T_world_cam, is_poseframe):
+        """One frame.  `img`: H x W uint8 (any row stride); returns the emitted features as a dict of arrays
+        (vtx n x 2, idepth_mu, idepth_var, slot, status)."""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 2 or img.shape != (self.H, self.W) or img.strides[1] != 1 or img.strides[0] < self.W:
+            raise ValueError("img must be H x W uint8 with unit pixel stride")
+        T = _pose(T_world_cam)
+        n = C.c_int32()
+        _l.check(self._lib.flame_hip_frontend_track(self._h, C.byref(params), C.c_void_p(img.ctypes.data), int(img.strides[0]),
+                                                    int(img_id), _ptr(T), int(bool(is_poseframe)), C.byref(n)),
+                 "flame_hip_frontend_track")
+        return self.features(n.value)
+
+    def features(self, n=None):
+        n = self.info("emitted") if n is None else n
+        out = dict(vtx=np.zeros((n, 2), np.float32), idepth_mu=np.zeros(n, np.float32), idepth_var=np.zeros(n, np.float32),
+                   slot=np.zeros(n, np.int32), status=np.zeros(n, np.int32))
+        _l.check(self._lib.flame_hip_frontend_features(self._h, n, _ptr(out["vtx"]), _ptr(out["idepth_mu"]), _ptr(out["idepth_var"]),
+                                                       _ptr(out["slot"]), _ptr(out["status"])), "flame_hip_frontend_features")
+        return out
+
+    def set_poses(self, ids, poses):
+        ids = np.ascontiguousarray(ids, np.uint32)
+        T = np.ascontiguousarray(np.concatenate([_pose(p) for p in poses]) if len(ids) else np.zeros(0))
+        _l.check(self._lib.flame_hip_frontend_set_poses(self._h, len(ids), _ptr(ids), _ptr(T)), "flame_hip_frontend_set_poses")
+
+    def prune(self, keep_ids):
+        ids = np.ascontiguousarray(keep_ids, np.uint32)
+        _l.check(self._lib.flame_hip_frontend_prune(self._h, len(ids), _ptr(ids)), "flame_hip_frontend_prune")
+
+    def info(self, key):
+        v = C.c_int64()
+        _l.check(self._lib.flame_hip_frontend_info(self._h, key.encode(), C.byref(v)), "flame_hip_frontend_info(%s)" % key)
+        return v.value
+
+    def state(self):
+        """Every slot's state (debug hook): dict of max_features-long arrays."""
+        F = self.max_features
+        s = dict(alive=np.zeros(F, np.uint8), u=np.zeros(F, np.int32), v=np.zeros(F, np.int32), pf=np.zeros(F, np.int32),
+                 mu=np.zeros(F, np.float32), var=np.zeros(F, np.float32), drop=np.zeros(F, np.int32),
+                 status=np.zeros(F, np.int32), kstar=np.zeros(F, np.int32))
+        _l.check(self._lib.flame_hip_frontend_state(self._h, *[_ptr(s[k]) for k in ("alive", "u", "v", "pf", "mu", "var", "drop",
+                                                                                    "status", "kstar")]), "flame_hip_frontend_state")
+        return s

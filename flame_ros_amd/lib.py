@@ -107,6 +107,15 @@ SYMBOLS = {
     "flame_hip_part_set_option": (C.c_int, [_VP, C.c_char_p, _I32]),
     "flame_hip_part_info": (C.c_int, [_VP, C.c_char_p, _I32, C.POINTER(_I64)]),
     "flame_hip_part_array": (_I64, [_VP, C.c_char_p, _I32, _VP, _I64]),
+    "flame_hip_frontend_default_params": (None, [_VP]),
+    "flame_hip_frontend_create": (C.c_int, [C.POINTER(_VP), C.c_int, _I32, _I32, _VP, _I32, _I32]),
+    "flame_hip_frontend_destroy": (None, [_VP]),
+    "flame_hip_frontend_track": (C.c_int, [_VP, _VP, _VP, _I32, C.c_uint32, _VP, _I32, C.POINTER(_I32)]),
+    "flame_hip_frontend_features": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "flame_hip_frontend_set_poses": (C.c_int, [_VP, _I32, _VP, _VP]),
+    "flame_hip_frontend_prune": (C.c_int, [_VP, _I32, _VP]),
+    "flame_hip_frontend_info": (C.c_int, [_VP, C.c_char_p, C.POINTER(_I64)]),
+    "flame_hip_frontend_state": (C.c_int, [_VP] + [_VP] * 9),
     "flame_hip_debug_plan_array": (_I64, [_VP, C.c_char_p, _VP, _I64]),
     "flame_hip_strerror": (C.c_char_p, [C.c_int]),
     "flame_hip_version": (C.c_int, []),

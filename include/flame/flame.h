@@ -18,7 +18,8 @@
 // per-triangle stage (a8), dense maps / mesh (f1, f2).  The feature pipeline plugs in through
 // FrontEnd (tracked features of the frame; optionally the triangulation of the gated features, whose
 // default is the library's exact Delaunay triangulation on the GPU, flame_hip_delaunay -- row f3's first leg --, or,
-// with Params::triangulate_on_gpu = false, the exact host triangulator of utils/delaunay.h);
+// with Params::triangulate_on_gpu = false, the exact host triangulator of utils/delaunay.h; flame/gpu_frontend.h is
+// a `track` that runs detection and epipolar tracking on the GPU, flame_hip_frontend_*);
 // update() returns false when no `track` is registered, exactly like any other failed update (the
 // frontends warn and skip the frame, src/flame_offline_tum.cc:597-601).  updateGraph() is the GPU
 // tail on its own, for callers that already hold features + triangulation.

@@ -1,0 +1,121 @@
+// include/flame/gpu_frontend.h -- the feature pipeline of flame::Flame::update() on the GPU: detection on a cell grid and
+// epipolar inverse-depth tracking (libflame_hip.so, flame_hip_frontend_*; the algorithm: DESIGN.md "Feature front end").
+//
+//   flame::Flame sensor(width, height, K, Kinv, params);
+//   flame::GpuFrontEnd features(width, height, K, params);
+//   sensor.setFrontEnd(features.frontEnd());
+//   sensor.update(time, img_id, pose, gray, is_poseframe);   // reference src/flame_offline_tum.cc:578-579
+//
+// frontEnd() binds `track`, `updatePoseFramePoses` and `prunePoseFrames` to this object (which must outlive the Flame it feeds);
+// `triangulate` stays empty, so the library's GPU Delaunay triangulation runs.  `track` hands every emitted feature of the frame
+// to Flame (whose variance gate selects the ones that enter the graph) and fails the frame when fewer than three are emitted.
+// Poses are T_world_cam; they cross into the library as row-major [R|t] in double, made from the unit quaternion and the
+// translation of SE3f (Sophus::SE3f when present, the fallback struct otherwise).  Nothing throws; a failure leaves its code
+// in lastError() (and the frame fails, which Flame reports like any failed update).
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <functional>
+#include <vector>
+
+#include "../flame_hip.h"
+#include "flame.h"
+#include "params.h"
+#include "types.h"
+
+namespace flame {
+
+class GpuFrontEnd {
+ public:
+  GpuFrontEnd(int width, int height, const Matrix3f& K, const Params& params = Params(), int max_features = 4096,
+              int max_poseframes = 16)
+      : width_(width), height_(height) {
+    float Kr[9];
+    toRowMajor(K, Kr);
+    flame_hip_frontend_default_params(&fparams_);
+    fparams_.detection_win_size = params.detection_win_size;
+    fparams_.min_grad_mag = params.min_grad_mag;
+    fparams_.win_size = params.zparams.win_size;
+    fparams_.epipolar_line_var = params.zparams.epipolar_line_var;
+    fparams_.max_dropouts = params.max_dropouts;
+    last_error_ = flame_hip_frontend_create(&handle_, params.hip_device, width, height, Kr, max_features, max_poseframes);
+    if (last_error_) handle_ = nullptr;
+  }
+  ~GpuFrontEnd() { flame_hip_frontend_destroy(handle_); }
+  GpuFrontEnd(const GpuFrontEnd&) = delete;
+  GpuFrontEnd& operator=(const GpuFrontEnd&) = delete;
+
+  // the front end's own parameters (search clamp, prior of a new feature, match threshold): change before the first frame
+  flame_hip_frontend_params& frontendParams() { return fparams_; }
+  int lastError() const { return last_error_; }
+  flame_hip_frontend* handle() const { return handle_; }
+
+  FrontEnd frontEnd() {
+    FrontEnd fe;
+    fe.track = [this](const FrameInput& in, FeatureSet* out) { return track(in, out); };
+    fe.updatePoseFramePoses = [this](const std::vector<uint32_t>& ids, const std::vector<SE3f>& poses) { updatePoseFramePoses(ids, poses); };
+    fe.prunePoseFrames = [this](const std::vector<uint32_t>& ids) { prunePoseFrames(ids); };
+    return fe;
+  }
+
+  bool track(const FrameInput& in, FeatureSet* out) {
+    if (!handle_) return false;  // (lastError() still holds why the handle could not be made)
+    if (!in.img || !out || in.img->rows != height_ || in.img->cols != width_) return fail(FLAME_HIP_ERR_ARG);
+    double T[12];
+    toRt(in.pose, T);
+    const uint8_t* row0 = in.img->ptr<uint8_t>(0);
+    const int32_t pitch = height_ > 1 ? static_cast<int32_t>(in.img->ptr<uint8_t>(1) - row0) : width_;
+    int32_t n = 0;
+    int rc = flame_hip_frontend_track(handle_, &fparams_, row0, pitch, in.img_id, T, in.is_poseframe ? 1 : 0, &n);
+    if (rc) return fail(rc);
+    static_assert(sizeof(Point2f) == 2 * sizeof(float), "boundary types are packed");
+    out->vtx.resize(static_cast<size_t>(n));
+    out->idepth_mu.resize(static_cast<size_t>(n));
+    out->idepth_var.resize(static_cast<size_t>(n));
+    out->prediction.clear();
+    rc = flame_hip_frontend_features(handle_, n, n ? reinterpret_cast<float*>(out->vtx.data()) : nullptr, out->idepth_mu.data(),
+                                     out->idepth_var.data(), nullptr, nullptr);
+    if (rc) return fail(rc);
+    last_error_ = 0;
+    return n >= 3;
+  }
+
+  void updatePoseFramePoses(const std::vector<uint32_t>& ids, const std::vector<SE3f>& poses) {
+    if (!handle_ || ids.size() != poses.size()) return;
+    std::vector<double> T(12 * ids.size());
+    for (size_t i = 0; i < ids.size(); ++i) toRt(poses[i], &T[12 * i]);
+    last_error_ = flame_hip_frontend_set_poses(handle_, static_cast<int32_t>(ids.size()), ids.data(), T.data());
+  }
+  void prunePoseFrames(const std::vector<uint32_t>& keep_ids) {
+    if (!handle_) return;
+    last_error_ = flame_hip_frontend_prune(handle_, static_cast<int32_t>(keep_ids.size()), keep_ids.data());
+  }
+
+  // [R|t], row-major 3x4 in double, from the pose's unit quaternion (normalised again in double) and translation
+  static void toRt(const SE3f& pose, double T[12]) {
+#ifdef FLAME_HAVE_SOPHUS
+    double x = pose.unit_quaternion().x(), y = pose.unit_quaternion().y(), z = pose.unit_quaternion().z(), w = pose.unit_quaternion().w();
+    const double t[3] = {pose.translation()(0), pose.translation()(1), pose.translation()(2)};
+#else
+    double x = pose.q[0], y = pose.q[1], z = pose.q[2], w = pose.q[3];
+    const double t[3] = {pose.t[0], pose.t[1], pose.t[2]};
+#endif
+    const double n = std::sqrt(((x * x + y * y) + z * z) + w * w);
+    x /= n; y /= n; z /= n; w /= n;
+    T[0] = 1.0 - 2.0 * (y * y + z * z); T[1] = 2.0 * (x * y - z * w);       T[2] = 2.0 * (x * z + y * w);        T[3] = t[0];
+    T[4] = 2.0 * (x * y + z * w);       T[5] = 1.0 - 2.0 * (x * x + z * z); T[6] = 2.0 * (y * z - x * w);        T[7] = t[1];
+    T[8] = 2.0 * (x * z - y * w);       T[9] = 2.0 * (y * z + x * w);       T[10] = 1.0 - 2.0 * (x * x + y * y); T[11] = t[2];
+  }
+
+ private:
+  bool fail(int code) {
+    last_error_ = code;
+    return false;
+  }
+  int width_, height_;
+  flame_hip_frontend_params fparams_;
+  flame_hip_frontend* handle_ = nullptr;
+  int last_error_ = 0;
+};
+
+}  // namespace flame

@@ -2,9 +2,10 @@
 //
 // Every field below is assigned from a rosparam by the reference frontends (reference
 // src/flame_offline_tum.cc:158-249, src/flame_offline_asl.cc, src/flame_nodelet.cc:220-330);
-// defaults are the values of cfg/flame_offline_tum.yaml.  Only the regulariser / triangle-filter
-// fields drive the HIP path; the rest are carried so the frontends compile and can be forwarded to
-// the upstream feature pipeline unchanged.
+// defaults are the values of cfg/flame_offline_tum.yaml.  The regulariser / triangle-filter fields
+// drive the GPU tail; min_grad_mag, detection_win_size, max_dropouts, zparams.win_size and
+// zparams.epipolar_line_var drive the GPU feature front end (flame/gpu_frontend.h); the rest are
+// carried so the frontends compile and can be forwarded to another feature pipeline unchanged.
 #pragma once
 
 namespace flame {

@@ -1,6 +1,7 @@
 /*
  * include/flame_hip.h -- C ABI of libflame_hip.so: FLaME's NLTGV2-L1 graph regulariser and
- * per-triangle stage as hand-written HIP kernels for MI355X (gfx950).
+ * per-triangle stage as hand-written HIP kernels for MI355X (gfx950), and the feature front end in
+ * front of them (detection + epipolar inverse-depth tracking, the flame_hip_frontend entry points below).
  *
  * This is the drop-in boundary.  Upstream, flame::Flame::update() (called at reference
  * src/flame_offline_tum.cc:578-579,593-594, src/flame_offline_asl.cc:520,535,
@@ -418,6 +419,69 @@ int flame_hip_part_info(const flame_hip_part* p, const char* key, int32_t local_
 /* int32 arrays: "part" (V: the part of every vertex), per local part "vid", "eid", "edges", "e_owned", "peers",
  * "send_v", "send_e", "recv_v", "recv_e", "send_cnt", "recv_cnt"; returns the element count or a negative error */
 int64_t flame_hip_part_array(const flame_hip_part* p, const char* key, int32_t local_part, int32_t* out, int64_t cap);
+
+/* ---- feature front end: what upstream's Flame::update() does in FRONT of the graph ("feature detect, epipolar
+ * idepth filter") -- a camera image and a pose in, the frame's features with inverse depths out.  Upstream's code for it is not
+ * in the reference tree; the algorithm is this build's own statement (DESIGN.md "Feature front end", [UPSTREAM-RECALL] where it
+ * follows the paper), restated operation by operation in tests/frontend_ref.py, which the GPU equals bit for bit.  In short:
+ * a feature lives at an integer pixel of a POSE FRAME with an inverse-depth prior (mu, var); every frame it is searched along
+ * its epipolar segment mu +- 2 sigma in the new image (<= 257 samples, <= 1 px apart unless the cap is hit; win x win SSD of
+ * 1/16-px bilinear samples as integers), the sub-sample minimum becomes an inverse-depth measurement that is fused into the
+ * prior, and the feature is projected into the current frame -- at most one per detection cell is emitted (smallest variance).
+ * On a pose frame every cell without an emitted feature gets a new one at its largest image gradient above min_grad_mag.
+ * The handle owns a ring of max_poseframes pose-frame images on the device and max_features feature slots; all float32, no
+ * fused multiply-add, integer costs.  One handle is not thread-safe.  The library reads no environment variable. */
+typedef struct flame_hip_frontend flame_hip_frontend; /* opaque; owns device buffers */
+typedef struct {
+  int32_t detection_win_size; /* flame::Params::detection_win_size (16): side of a detection cell */
+  float min_grad_mag;         /* Params::min_grad_mag (5): central-difference gradient magnitude a detection needs */
+  int32_t win_size;           /* Params::zparams.win_size (5): matching window, odd, <= 9 */
+  float epipolar_line_var;    /* Params::zparams.epipolar_line_var (4): px^2 of a match along the epipolar line */
+  int32_t max_dropouts;       /* Params::max_dropouts (5): a feature dies when it fails more often than this in a row */
+  float idepth_min, idepth_max; /* search interval clamp (0.01, 10) */
+  float idepth_init, var_init;  /* prior of a new feature (0.5, 0.25) */
+  float max_match_error;        /* grey^2 per window pixel above which the best match is rejected (100) */
+} flame_hip_frontend_params;
+/* status of a feature in its last frame; the first four failures are in the order they are tested */
+enum {
+  FLAME_HIP_FE_OK = 0,          /* matched, measurement fused, dropout counter cleared */
+  FLAME_HIP_FE_NO_PARALLAX = 1, /* the search segment is shorter than 2 px: state and counter untouched */
+  FLAME_HIP_FE_OUTSIDE = 2,     /* no sample's window lies inside the image (or the segment leaves the camera's front) */
+  FLAME_HIP_FE_BAD_MATCH = 3,   /* best cost above max_match_error (or a degenerate measurement) */
+  FLAME_HIP_FE_AMBIGUOUS = 4,   /* a sample more than 2 steps from the best costs less than 1.5 x the best */
+  FLAME_HIP_FE_NEW = 5,         /* detected in this (pose) frame */
+  FLAME_HIP_FE_DIED = 6         /* dropout counter exceeded max_dropouts in this frame: the slot is free again */
+};
+void flame_hip_frontend_default_params(flame_hip_frontend_params* p);
+/* K row-major 3x3 pinhole (fx = K[0], fy = K[4], cx = K[2], cy = K[5]); images arrive rectified.  8 <= W, H <= 8192;
+ * max_poseframes <= 64.  Device memory: (max_poseframes + 1) W H bytes + ~100 bytes per feature slot. */
+int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, int32_t H, const float K[9], int32_t max_features,
+                              int32_t max_poseframes);
+void flame_hip_frontend_destroy(flame_hip_frontend* fe);
+/* One frame: img = H rows of W grey bytes, `pitch` bytes apart (any pitch >= W, any alignment); T_world_cam = row-major 3x4
+ * [R|t] in double.  Uploads the image, tracks every live feature against it, projects them, on a pose frame detects new ones
+ * (the image joins the ring under img_id, overwriting the oldest slot once the ring is full: the features of the overwritten
+ * pose frame die first), compacts the emitted features in ascending slot order and returns when *n_out and the features are
+ * on the host.  Errors: ARG (NULL, pitch < W, win_size even or > 9, ...), NAN (non-finite pose or parameter). */
+int flame_hip_frontend_track(flame_hip_frontend* fe, const flame_hip_frontend_params* params, const uint8_t* img, int32_t pitch,
+                             uint32_t img_id, const double T_world_cam[12], int32_t is_poseframe, int32_t* n_out);
+/* The features the last frame emitted (cap >= n_out; any pointer may be NULL): vtx 2 per feature (pixel in the CURRENT frame),
+ * inverse depth and variance in the current frame, slot, status (FLAME_HIP_FE_*). */
+int flame_hip_frontend_features(flame_hip_frontend* fe, int32_t cap, float* vtx, float* idepth_mu, float* idepth_var, int32_t* slot,
+                                int32_t* status);
+/* flame::Flame::updatePoseFramePoses / prunePoseFrames (reference src/flame_nodelet.cc:474-475): new world poses (12 doubles
+ * each) of pose frames by id, ids the ring does not hold are ignored; keep only the listed pose frames -- the features of
+ * every other pose frame die. */
+int flame_hip_frontend_set_poses(flame_hip_frontend* fe, int32_t n, const uint32_t* ids, const double* T);
+int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* keep_ids);
+/* keys: "live", "poseframes", "emitted", "track_us" (host time of the last frame's call), "track_device_us" (HIP events around
+ * its device work); features of the last frame per status: "ok", "no_parallax", "outside", "bad_match", "ambiguous", "new",
+ * "died"; "detections_dropped" (no free slot), "max_features" */
+int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value);
+/* Debug/test hook: every slot's state (max_features entries each; any pointer may be NULL): alive, reference pixel (u, v),
+ * ring slot of its pose frame, prior (mu, var) in the pose frame, dropout counter, last status (-1 = free), last best sample. */
+int flame_hip_frontend_state(flame_hip_frontend* fe, uint8_t* alive, int32_t* u, int32_t* v, int32_t* poseframe, float* mu, float* var,
+                             int32_t* dropouts, int32_t* status, int32_t* kstar);
 
 /* Debug/test hook (no device needed; works on a handle created with device = -1): copies the
  * named host-side plan array ("v_o2i", "e_o2i", "grow", "ginc", "eij", "tiles", "t_vmap",

@@ -1,0 +1,360 @@
+"""The feature front end's algorithm statement (DESIGN.md "Feature front end") restated in NumPy: np.float32 scalars in
+the kernels' operation order (no fused multiply-add exists here), Python integers for the image costs.  The GPU
+(flame_ros_amd/csrc/frontend.hip behind flame_hip_frontend_*) must equal this BIT FOR BIT: slots, statuses, k*, mu, var and
+the emitted features.  tests/test_frontend_ref.py checks this file against ground truth, so that "GPU equals
+restatement" is not circular.  Also the synthetic scenes both test files use.
+"""
+import math
+
+import numpy as np
+
+F = np.float32
+OK, NO_PARALLAX, OUTSIDE, BAD_MATCH, AMBIGUOUS, NEW, DIED, FREE = 0, 1, 2, 3, 4, 5, 6, -1
+MAX_SAMPLES = 256
+DEFAULTS = dict(detection_win_size=16, min_grad_mag=5.0, win_size=5, epipolar_line_var=4.0, max_dropouts=5,
+                idepth_min=0.01, idepth_max=10.0, idepth_init=0.5, var_init=0.25, max_match_error=100.0)
+
+
+def params(**kw):
+    p = dict(DEFAULTS)
+    for k in kw:
+        assert k in p, k
+    p.update(kw)
+    return p
+
+
+def pose_record(K4, Tc, Tr):
+    """A = K R, c = K t of T_cur_ref = T_world_cur^-1 T_world_ref in double (sums left to right), rounded once to
+    float32.  Tc / Tr: 3x4 [R|t] float64."""
+    fx, fy, cx, cy = (float(x) for x in K4)
+    Tc = [[float(x) for x in row] for row in np.asarray(Tc, np.float64).reshape(3, 4)]
+    Tr = [[float(x) for x in row] for row in np.asarray(Tr, np.float64).reshape(3, 4)]
+    R = [[(Tc[0][i] * Tr[0][j] + Tc[1][i] * Tr[1][j]) + Tc[2][i] * Tr[2][j] for j in range(3)] for i in range(3)]
+    d = [Tr[k][3] - Tc[k][3] for k in range(3)]
+    t = [(Tc[0][i] * d[0] + Tc[1][i] * d[1]) + Tc[2][i] * d[2] for i in range(3)]
+    A = [[F(fx * R[0][j] + cx * R[2][j]) for j in range(3)], [F(fy * R[1][j] + cy * R[2][j]) for j in range(3)],
+         [F(R[2][j]) for j in range(3)]]
+    c = [F(fx * t[0] + cx * t[2]), F(fy * t[1] + cy * t[2]), F(t[2])]
+    return A, c
+
+
+def quat_pose(q_xyzw, t):
+    """[R|t] in double from a float32 unit quaternion (x, y, z, w) and translation, as include/flame/gpu_frontend.h does it."""
+    x, y, z, w = (float(F(a)) for a in q_xyzw)
+    n = math.sqrt(((x * x + y * y) + z * z) + w * w)
+    x, y, z, w = x / n, y / n, z / n, w / n
+    R = [[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)],
+         [2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)],
+         [2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)]]
+    return np.array([R[i] + [float(F(t[i]))] for i in range(3)], np.float64)
+
+
+def g2_image(img):
+    """Squared central-difference gradient as integers; the one-pixel border is 0 (never a candidate: m >= 1)."""
+    I = img.astype(np.int64)
+    g2 = np.zeros(I.shape, np.int64)
+    g2[1:-1, 1:-1] = (I[1:-1, 2:] - I[1:-1, :-2]) ** 2 + (I[2:, 1:-1] - I[:-2, 1:-1]) ** 2
+    return g2
+
+
+def g2_threshold(min_grad_mag):
+    return max(1, int(math.ceil(4.0 * float(F(min_grad_mag)) * float(F(min_grad_mag)))))
+
+
+def _finite(x):
+    return bool(np.isfinite(x))
+
+
+class FrontEndRef:
+    """Same calls and the same state as a flame_hip_frontend handle."""
+
+    def __init__(self, W, H, K, max_features=2048, max_poseframes=8):
+        K = np.asarray(K, np.float32).reshape(9)
+        self.W, self.H, self.F, self.P = W, H, max_features, max_poseframes
+        self.K4 = (K[0], K[4], K[2], K[5])
+        self.pf_used = [False] * max_poseframes
+        self.pf_id = [0] * max_poseframes
+        self.pf_T = [None] * max_poseframes
+        self.pf_img = [None] * max_poseframes
+        self.pf_added = 0
+        n = max_features
+        self.alive = np.zeros(n, np.uint8)
+        self.u, self.v, self.pf, self.drop = (np.zeros(n, np.int32) for _ in range(4))
+        self.mu, self.var = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        self.status, self.kstar = np.full(n, FREE, np.int32), np.full(n, -1, np.int32)
+        self.pstar = np.full((n, 2), np.nan, np.float32)  # matched position of the last OK frame (for the ground-truth tests)
+        self.steps = np.zeros(n, np.int32)                # S of the last search (for the tests' own sanity checks)
+        self.counts = {}
+
+    # ---- one sample's cost ----
+    def _cost(self, cur, ref, u, v, px, py, win):
+        r = win // 2
+        fqx, fqy = np.floor(px * F(16.0) + F(0.5)), np.floor(py * F(16.0) + F(0.5))
+        if not (fqx >= 0 and fqx <= F(16 * self.W) and fqy >= 0 and fqy <= F(16 * self.H)):
+            return None
+        qx, qy = int(fqx), int(fqy)
+        ix, iy = qx >> 4, qy >> 4
+        if ix - r < 0 or iy - r < 0 or ix + r + 1 > self.W - 1 or iy + r + 1 > self.H - 1:
+            return None
+        wx1, wy1 = qx & 15, qy & 15
+        wx0, wy0 = 16 - wx1, 16 - wy1
+        c = cur[iy - r:iy + r + 2, ix - r:ix + r + 2]
+        D = (wx0 * wy0) * c[:-1, :-1] + (wx1 * wy0) * c[:-1, 1:] + (wx0 * wy1) * c[1:, :-1] + (wx1 * wy1) * c[1:, 1:] \
+            - 256 * ref[v - r:v + r + 1, u - r:u + r + 1]
+        return int((D * D).sum())
+
+    # ---- track + project one live feature; returns (cell, proj) or None ----
+    def _track_one(self, s, p, cur, poses):
+        W, H, win = self.W, self.H, p["win_size"]
+        fx, fy, cx, cy = self.K4
+        u, v, f = int(self.u[s]), int(self.v[s]), int(self.pf[s])
+        mu, var, drop = self.mu[s], self.var[s], int(self.drop[s])
+        A, c = poses[f]
+        ref = self.pf_img[f]
+        b0, b1 = (F(u) - cx) / fx, (F(v) - cy) / fy
+        a0 = (A[0][0] * b0 + A[0][1] * b1) + A[0][2]
+        a1 = (A[1][0] * b0 + A[1][1] * b1) + A[1][2]
+        a2 = (A[2][0] * b0 + A[2][1] * b1) + A[2][2]
+        c0, c1, c2 = c
+        two = F(2.0) * np.sqrt(var)
+        lo, hi = mu - two, mu + two
+        idmin, idmax = F(p["idepth_min"]), F(p["idepth_max"])
+        xi0 = lo if lo > idmin else idmin
+        xi1 = hi if hi < idmax else idmax
+        d0, d1 = a2 + xi0 * c2, a2 + xi1 * c2
+        r = win // 2
+        ref_in = u - r >= 0 and v - r >= 0 and u + r <= W - 1 and v + r <= H - 1
+        ks = -1
+        mu_new, var_new = mu, var
+        if not (d0 > 0 and d1 > 0) or not ref_in:
+            status = OUTSIDE
+        else:
+            x0, y0 = (a0 + xi0 * c0) / d0, (a1 + xi0 * c1) / d0
+            x1, y1 = (a0 + xi1 * c0) / d1, (a1 + xi1 * c1) / d1
+            dx, dy = x1 - x0, y1 - y0
+            L = np.sqrt(dx * dx + dy * dy)
+            if not (L >= F(2.0)):
+                status = NO_PARALLAX
+            else:
+                S = MAX_SAMPLES if L >= F(MAX_SAMPLES) else int(np.ceil(L))
+                ex, ey = dx / F(S), dy / F(S)
+                self.steps[s] = S
+                C = [self._cost(cur, ref, u, v, x0 + F(k) * ex, y0 + F(k) * ey, win) for k in range(S + 1)]
+                valid = [k for k in range(S + 1) if C[k] is not None]
+                if not valid:
+                    status = OUTSIDE
+                else:
+                    ks = min(valid, key=lambda k: (C[k], k))
+                    Cb = C[ks]
+                    bad = int(float(F(p["max_match_error"])) * float(win * win) * 65536.0)
+                    if Cb > bad:
+                        status = BAD_MATCH
+                    elif any(abs(k - ks) > 2 and 2 * C[k] < 3 * Cb for k in valid):
+                        status = AMBIGUOUS
+                    else:
+                        Cm = C[ks - 1] if ks > 0 else None
+                        Cp = C[ks + 1] if ks + 1 <= S else None
+                        delta = F(0.0)
+                        if Cm is not None and Cp is not None:
+                            fm, f0, fp = F(Cm), F(Cb), F(Cp)
+                            den = (fm - F(2.0) * f0) + fp
+                            if den > 0:
+                                delta = (F(0.5) * (fm - fp)) / den
+                        t = F(ks) + delta
+                        xs, ys = x0 + t * ex, y0 + t * ey
+                        if abs(ex) >= abs(ey):
+                            xp, xn = xs + ex, xs - ex
+                            xi_m = (a0 - xs * a2) / (xs * c2 - c0)
+                            xi_p = (a0 - xp * a2) / (xp * c2 - c0)
+                            xi_n = (a0 - xn * a2) / (xn * c2 - c0)
+                        else:
+                            yp, yn = ys + ey, ys - ey
+                            xi_m = (a1 - ys * a2) / (ys * c2 - c1)
+                            xi_p = (a1 - yp * a2) / (yp * c2 - c1)
+                            xi_n = (a1 - yn * a2) / (yn * c2 - c1)
+                        sl = (xi_p - xi_n) * F(0.5)
+                        var_m = (sl * sl) * F(p["epipolar_line_var"])
+                        den = var + var_m
+                        mu_f = (mu * var_m + xi_m * var) / den
+                        var_f = (var * var_m) / den
+                        if _finite(xi_m) and _finite(var_m) and _finite(mu_f) and _finite(var_f):
+                            status, mu_new, var_new = OK, mu_f, var_f
+                            self.pstar[s] = (xs, ys)
+                        else:
+                            status = BAD_MATCH
+        failed = status in (OUTSIDE, BAD_MATCH, AMBIGUOUS)
+        if status == OK:
+            mu, var, drop = mu_new, var_new, 0
+        w0, w1, w2 = a0 + mu * c0, a1 + mu * c1, a2 + mu * c2
+        pok, proj = False, None
+        if w2 > 0:
+            px, py, xc = w0 / w2, w1 / w2, mu / w2
+            g = a2 / (w2 * w2)
+            vc = var * (g * g)
+            pok = bool(px >= 0 and px <= F(W - 1) and py >= 0 and py <= F(H - 1) and _finite(xc) and _finite(vc) and vc >= 0)
+            proj = (px, py, xc, vc)
+        if failed or not pok:
+            drop += 1
+        self.mu[s], self.var[s], self.drop[s], self.kstar[s] = mu, var, drop, ks
+        self.counts[status] = self.counts.get(status, 0) + 1
+        if drop > p["max_dropouts"]:
+            self.alive[s], self.status[s] = 0, DIED
+            self.counts[DIED] = self.counts.get(DIED, 0) + 1
+            return None
+        self.status[s] = status
+        if not pok:
+            return None
+        dws = p["detection_win_size"]
+        ncx = (W + dws - 1) // dws
+        return (int(py) // dws) * ncx + int(px) // dws, proj
+
+    def track(self, p, img, img_id, T_world_cam, is_poseframe):
+        W, H, win, dws = self.W, self.H, p["win_size"], p["detection_win_size"]
+        img = np.ascontiguousarray(img, np.uint8)
+        assert img.shape == (H, W)
+        cur = img.astype(np.int64)
+        T = np.asarray(T_world_cam, np.float64).reshape(3, 4)
+        self.counts = {}
+        cur_pf = -1
+        if is_poseframe:
+            cur_pf = self.pf_added % self.P
+            if self.pf_used[cur_pf]:
+                self.pf_used[cur_pf] = False
+                self._kill()
+        poses = [pose_record(self.K4, T, self.pf_T[q]) if self.pf_used[q] else None for q in range(self.P)]
+        ncx, ncy = (W + dws - 1) // dws, (H + dws - 1) // dws
+        cell_key = {}
+        cell_of, proj = {}, {}
+        with np.errstate(all="ignore"):
+            for s in range(self.F):
+                if not self.alive[s]:
+                    self.status[s], self.kstar[s] = FREE, -1
+                    continue
+                res = self._track_one(s, p, cur, poses)
+                if res is not None:
+                    cell, pr = res
+                    key = (int(np.float32(pr[3]).view(np.uint32)), s)
+                    if cell not in cell_key or key < cell_key[cell]:
+                        cell_key[cell] = key
+                    cell_of[s], proj[s] = cell, pr
+        n_new = dropped = 0
+        if is_poseframe:
+            g2 = g2_image(img)
+            thr, m = g2_threshold(p["min_grad_mag"]), win // 2 + 1
+            free = [s for s in range(self.F) if not self.alive[s]]
+            for cell in range(ncx * ncy):
+                if cell in cell_key:
+                    continue
+                ccx, ccy = cell % ncx, cell // ncx
+                xlo, xhi = max(ccx * dws, m), min(ccx * dws + dws, W - m)
+                ylo, yhi = max(ccy * dws, m), min(ccy * dws + dws, H - m)
+                if xhi <= xlo or yhi <= ylo:
+                    continue
+                sub = g2[ylo:yhi, xlo:xhi]
+                i = int(np.argmax(sub))  # first maximum in row-major order: smallest y, then smallest x
+                if sub.flat[i] < thr:
+                    continue
+                if n_new >= len(free):
+                    dropped += 1
+                    continue
+                s = free[n_new]
+                n_new += 1
+                y, x = ylo + i // (xhi - xlo), xlo + i % (xhi - xlo)
+                self.alive[s], self.u[s], self.v[s], self.pf[s], self.drop[s] = 1, x, y, cur_pf, 0
+                self.mu[s], self.var[s] = F(p["idepth_init"]), F(p["var_init"])
+                self.status[s], self.kstar[s] = NEW, -1
+                cell_of[s], proj[s] = cell, (F(x), F(y), F(p["idepth_init"]), F(p["var_init"]))
+                cell_key[cell] = (int(F(p["var_init"]).view(np.uint32)), s)
+            self.pf_used[cur_pf], self.pf_id[cur_pf], self.pf_T[cur_pf], self.pf_img[cur_pf] = True, int(img_id), T.copy(), cur
+            self.pf_added += 1
+        self.counts[NEW], self.dropped = n_new, dropped
+        em = [s for s in sorted(cell_of) if self.alive[s] and cell_key[cell_of[s]][1] == s]
+        return dict(vtx=np.array([[proj[s][0], proj[s][1]] for s in em], np.float32).reshape(-1, 2),
+                    idepth_mu=np.array([proj[s][2] for s in em], np.float32), idepth_var=np.array([proj[s][3] for s in em], np.float32),
+                    slot=np.array(em, np.int32), status=np.array([self.status[s] for s in em], np.int32))
+
+    def _kill(self):
+        for s in range(self.F):
+            if self.alive[s] and not self.pf_used[self.pf[s]]:
+                self.alive[s] = 0
+
+    def set_poses(self, ids, poses):
+        for i, T in zip(ids, poses):
+            for q in range(self.P):
+                if self.pf_used[q] and self.pf_id[q] == int(i):
+                    self.pf_T[q] = np.asarray(T, np.float64).reshape(3, 4).copy()
+
+    def prune(self, keep_ids):
+        keep = set(int(i) for i in keep_ids)
+        for q in range(self.P):
+            if self.pf_used[q] and self.pf_id[q] not in keep:
+                self.pf_used[q] = False
+        self._kill()
+
+    def state(self):
+        return dict(alive=self.alive.copy(), u=self.u.copy(), v=self.v.copy(), pf=self.pf.copy(), mu=self.mu.copy(),
+                    var=self.var.copy(), drop=self.drop.copy(), status=self.status.copy(), kstar=self.kstar.copy())
+
+
+# ---------------------------------------------------------------- scenes ----
+
+def pose(t=(0.0, 0.0, 0.0), yaw=0.0):
+    """T_world_cam [R|t]: rotation by `yaw` about the camera's y axis."""
+    c, s = math.cos(yaw), math.sin(yaw)
+    return np.array([[c, 0.0, s, t[0]], [0.0, 1.0, 0.0, t[1]], [-s, 0.0, c, t[2]]], np.float64)
+
+
+def upsampled_texture(h, w, seed, factor=8):
+    """A random grey texture, `factor` x bilinearly upsampled, at least h x w, uint8."""
+    rng = np.random.default_rng(seed)
+    lh, lw = h // factor + 3, w // factor + 3
+    low = rng.integers(0, 256, (lh, lw)).astype(np.float64)
+    ys, xs = np.arange((lh - 1) * factor) / factor, np.arange((lw - 1) * factor) / factor
+    y0, x0 = ys.astype(int), xs.astype(int)
+    fy, fx = (ys - y0)[:, None], (xs - x0)[None, :]
+    up = (1 - fy) * (1 - fx) * low[y0][:, x0] + (1 - fy) * fx * low[y0][:, x0 + 1] + fy * (1 - fx) * low[y0 + 1][:, x0] + \
+        fy * fx * low[y0 + 1][:, x0 + 1]
+    return np.floor(up + 0.5).astype(np.uint8)[:h, :w]
+
+
+SCENE_W, SCENE_H, SCENE_F = 160, 120, 140.0
+SCENE_K = np.array([SCENE_F, 0, 79.5, 0, SCENE_F, 59.5, 0, 0, 1], np.float32)
+
+
+def shift_scene(D, seed, Z=2.0, W=SCENE_W, H=SCENE_H, big=None):
+    """Scene (a): a fronto-parallel plane at depth Z before and after a sideways translation of D Z / f -- the second
+    image is the first one D pixels further along the texture.  Returns [(img, T_world_cam)] x 2."""
+    big = upsampled_texture(H, W + D, seed) if big is None else big
+    return [(np.ascontiguousarray(big[:H, :W]), pose()),
+            (np.ascontiguousarray(big[:H, D:D + W]), pose((D * Z / SCENE_F, 0.0, 0.0)))]
+
+
+PLANE_N, PLANE_DEPTH = np.array([0.2, -0.1, 1.0]), 3.0
+
+
+def plane_idepth(T, x, y):
+    """True inverse depth of the slanted plane at pixel (x, y) (arrays) of the camera at T_world_cam."""
+    T = np.asarray(T, np.float64).reshape(3, 4)
+    fx, fy, cx, cy = SCENE_F, SCENE_F, float(SCENE_K[2]), float(SCENE_K[5])
+    ray = np.stack([(x - cx) / fx, (y - cy) / fy, np.ones_like(x, dtype=np.float64)], -1) @ T[:, :3].T
+    s = (PLANE_N @ np.array([0.0, 0.0, PLANE_DEPTH]) - PLANE_N @ T[:, 3]) / (ray @ PLANE_N)
+    return 1.0 / s, T[:, 3] + s[..., None] * ray
+
+
+def plane_scene(seed, frames=6):
+    """Scene (b): the plane through (0, 0, 3) with normal (0.2, -0.1, 1), textured at 3 texels per world unit (bilinear),
+    rendered analytically from `frames` poses: 0.03 sideways and 0.004 rad per frame."""
+    rng = np.random.default_rng(seed)
+    low = rng.integers(0, 256, (64, 64)).astype(np.float64)
+    yy, xx = np.mgrid[0:SCENE_H, 0:SCENE_W].astype(np.float64)
+    out = []
+    for k in range(frames):
+        T = pose((0.03 * k, 0.0, 0.0), 0.004 * k)
+        _, X = plane_idepth(T, xx, yy)
+        tu, tv = 3.0 * X[..., 0] + 32.0, 3.0 * X[..., 1] + 32.0
+        u0, v0 = np.floor(tu).astype(int), np.floor(tv).astype(int)
+        fu, fv = tu - u0, tv - v0
+        val = (1 - fv) * (1 - fu) * low[v0, u0] + (1 - fv) * fu * low[v0, u0 + 1] + fv * (1 - fu) * low[v0 + 1, u0] + \
+            fv * fu * low[v0 + 1, u0 + 1]
+        out.append((np.floor(val + 0.5).astype(np.uint8), T))
+    return out

@@ -7,8 +7,8 @@
 // dataset index -> image files -> pixels (include/flame_ros/dataset_streams.h, image_io.h) -> flame::Flame::update()
 // with a registered FrontEnd -> idepth mesh + stats per frame.
 //
-// Upstream's feature pipeline (detection, epipolar tracking) is not part of this build and plugs in through
-// flame::FrontEnd.  The stand-in used here is deliberately simple and says so: one feature per detection_win_size
+// The feature pipeline (detection, epipolar tracking) plugs in through flame::FrontEnd; this tool does not use the GPU
+// one (flame/gpu_frontend.h) yet.  The stand-in used here is deliberately simple and says so: one feature per detection_win_size
 // cell (cfg/flame_offline_tum.yaml:78) where the dataset's DEPTH image is valid, idepth = 1 / depth at that pixel
 // (what analysis/pass_in_truth feeds, src/flame_offline_tum.cc:577-595).  The kept features are triangulated by the
 // facade's built-in Delaunay triangulator (flame/utils/delaunay.h); everything behind the FrontEnd is the product path.

@@ -1,0 +1,67 @@
+"""Cost of the feature front end per frame: microseconds per flame_hip_frontend_track at 640x480 with ~1 200 live features,
+for a tracking frame and for a pose frame.  Recorded beside the from-features frame time of bench.py, not part of it.
+
+A ring of ONE pose frame makes every pose-frame call start from scratch (the features of the overwritten pose frame die, every
+cell detects again), so the two calls of a pair do the same work every time: the pose frame = upload + detection in all 1 200
+cells + slot assignment + compaction; the tracking frame = upload + 1 200 searches with the widest prior a feature ever has
+(var_init: ~16 samples of 5x5 pixels each) + projection + compaction.  Both are upper bounds of a running sequence, where
+most priors are narrower.  Times: HIP events around the call's device work (image upload to counts download) and the host's
+wall time of the whole call, median over the pairs after a warm-up.
+
+    python tools/frontend_bench.py [--frames 100] [--warmup 10]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def texture(h, w, seed=5, factor=8):
+    rng = np.random.default_rng(seed)
+    low = rng.integers(0, 256, (h // factor + 3, w // factor + 3)).astype(np.float32)
+    ys, xs = np.arange(h) / factor, np.arange(w) / factor
+    y0, x0 = ys.astype(int), xs.astype(int)
+    fy, fx = (ys - y0)[:, None], (xs - x0)[None, :]
+    up = (1 - fy) * (1 - fx) * low[y0][:, x0] + (1 - fy) * fx * low[y0][:, x0 + 1] + fy * (1 - fx) * low[y0 + 1][:, x0] + \
+        fy * fx * low[y0 + 1][:, x0 + 1]
+    return np.floor(up + 0.5).astype(np.uint8)
+
+
+def run(frames=100, warmup=10, W=640, H=480, shift=6):
+    from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
+    K = np.array([525, 0, 319.5, 0, 525, 239.5, 0, 0, 1], np.float32)
+    big = texture(H, W + shift)
+    a, b = np.ascontiguousarray(big[:, :W]), np.ascontiguousarray(big[:, shift:])
+    Ta = np.hstack([np.eye(3), np.zeros((3, 1))])
+    Tb = Ta.copy()
+    Tb[0, 3] = shift * 2.0 / 525.0  # the plane at depth 2 moved `shift` pixels
+    p = default_frontend_params()
+    t = {"poseframe": {"device": [], "host": []}, "tracking": {"device": [], "host": []}}
+    with GpuFrontEnd(W, H, K, max_features=2048, max_poseframes=1) as fe:
+        live = ok = 0
+        for i in range(warmup + frames):
+            for kind, img, T, pf in (("poseframe", a, Ta, True), ("tracking", b, Tb, False)):
+                fe.track(p, img, 2 * i + (not pf), T, pf)
+                if i >= warmup:
+                    t[kind]["device"].append(fe.info("track_device_us"))
+                    t[kind]["host"].append(fe.info("track_us"))
+            live, ok = fe.info("live"), fe.info("ok")
+    res = {"width": W, "height": H, "live_features": live, "matched_ok": ok, "pairs": frames}
+    for kind in t:
+        res[kind + "_device_us"] = float(np.median(t[kind]["device"]))
+        res[kind + "_host_us"] = float(np.median(t[kind]["host"]))
+    return res
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    a = ap.parse_args()
+    print(json.dumps({"frontend_track": run(max(a.frames, 50), a.warmup)}))
