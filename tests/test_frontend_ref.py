@@ -2,15 +2,17 @@
 "the GPU equals the restatement bit for bit" (tests/test_gpu_frontend.py) from being circular.
 
 (a) exact-shift scene: matched disparity against the true shift; (b) slanted plane over six frames: inverse depths against
-the analytic plane; (c) properties that need no reference."""
+the analytic plane, and the same plane under general motion (tests/frontend_scenes.py); (c) properties that need no reference.
+The per-feature float64 statement with rounding bands is tests/test_frontend_f64.py."""
 import numpy as np
 import pytest
 
 from tests import frontend_ref as R
+from tests import frontend_scenes as SC
 
 
-def run(frames, poseframes=(0,), max_features=256, max_poseframes=4, W=R.SCENE_W, H=R.SCENE_H, **kw):
-    fe = R.FrontEndRef(W, H, R.SCENE_K, max_features, max_poseframes)
+def run(frames, poseframes=(0,), max_features=256, max_poseframes=4, W=R.SCENE_W, H=R.SCENE_H, K=R.SCENE_K, **kw):
+    fe = R.FrontEndRef(W, H, K, max_features, max_poseframes)
     p = R.params(**kw)
     outs, states = [], []
     for k, (img, T) in enumerate(frames):
@@ -69,6 +71,49 @@ def test_slanted_plane_converges(seed):
     assert gated.sum() >= 3
     truth5, _ = R.plane_idepth(frames[5][1], o["vtx"][gated, 0].astype(np.float64), o["vtx"][gated, 1].astype(np.float64))
     assert np.median(np.abs(o["idepth_mu"][gated] - truth5) / truth5) <= 0.023
+
+
+# scene -> (worst median relative error of the state, worst share of var < 0.01, worst median relative error of the emitted,
+# gated features), each the worst over seeds 1 / 2 / 3 of the unmutated float32 restatement on the CPU
+GENERAL_MOTION = {
+    "sideways": (0.0098, 0.925, 0.0093),             # 0.93 / 0.98 / 0.80 %, 0.988 / 0.925 / 0.935, 0.80 / 0.93 / 0.74 %
+    "vertical": (0.0093, 0.922, 0.0077),             # 0.93 / 0.81 / 0.83 %, 0.975 / 0.963 / 0.922, 0.73 / 0.77 / 0.66 %
+    "diagonal_roll": (0.0098, 0.857, 0.0079),        # 0.94 / 0.71 / 0.98 %, 0.925 / 0.900 / 0.857, 0.79 / 0.61 / 0.70 %
+    "forward": (0.0219, 0.649, 0.0077),              # 2.11 / 1.48 / 2.19 %, 0.738 / 0.750 / 0.649, 0.73 / 0.75 / 0.77 %
+    "backward_side": (0.0168, 0.762, 0.0152),        # 1.68 / 1.29 / 1.59 %, 0.762 / 0.787 / 0.818, 1.52 / 0.94 / 1.18 %
+    "refpose_nonidentity": (0.0084, 0.878, 0.0074),  # 0.72 / 0.75 / 0.84 %, 0.910 / 0.911 / 0.878, 0.73 / 0.74 / 0.58 %
+}
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+@pytest.mark.parametrize("name", SC.NAMES)
+def test_general_motion_plane_converges(name, seed):
+    """The slanted plane under general motion (tests/frontend_scenes.py: fx != fy, an off-centre principal point, vertical,
+    forward and backward motion, roll, a reference pose that is not the identity), six frames, frame 0 the pose frame.
+    After frame 5 the unmutated float32 restatement measured the figures beside GENERAL_MOTION (live features 74-80, gated
+    emitted features 30-62).  Bounds, by this file's rule: median relative inverse-depth error <= twice the worst measured
+    over the seeds, share of live features with var < 0.01 >= the worst measured - 0.1, live >= 60; the emitted, gated
+    features against the plane seen from pose 5: <= twice their worst measured median, at least 15 of them (half the fewest
+    measured)."""
+    worst_err, worst_share, worst_emitted = GENERAL_MOTION[name]
+    frames = SC.scene(name, seed)
+    fe, outs, st = run(frames, K=SC.K)
+    s = st[5]
+    al = np.flatnonzero(s["alive"])
+    truth, _ = SC.plane_idepth(SC.K4, frames[0][1], s["u"][al], s["v"][al])
+    rel = np.abs(s["mu"][al] - truth) / truth
+    share = float((s["var"][al] < 0.01).mean())
+    o = outs[5]
+    gated = o["idepth_var"] < 0.01
+    truth5, _ = SC.plane_idepth(SC.K4, frames[5][1], o["vtx"][gated, 0], o["vtx"][gated, 1])
+    rel5 = np.abs(o["idepth_mu"][gated] - truth5) / truth5
+    print("%s seed %d: live %d median rel error %.4f share %.3f; emitted gated %d median rel error %.4f" % (
+        name, seed, len(al), np.median(rel), share, gated.sum(), np.median(rel5)))
+    assert len(al) >= 60
+    assert np.median(rel) <= 2.0 * worst_err
+    assert share >= worst_share - 0.1
+    assert gated.sum() >= 15
+    assert np.median(rel5) <= 2.0 * worst_emitted
 
 
 def brute_detections(img, win, dws, min_grad_mag):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import frontend_ref as R
+from tests import frontend_scenes as SC
 
 pytestmark = pytest.mark.gpu
 
@@ -99,6 +100,17 @@ def test_slanted_plane_six_frames(pair):
     for k, (img, T) in enumerate(R.plane_scene(1)):
         o = p.track(img, T, k == 0)
     assert (o["idepth_var"] < 0.01).sum() >= 30
+
+
+@pytest.mark.parametrize("name", SC.NAMES)
+def test_general_motion_scenes(pair, name):
+    """The six general-motion scenes (fx != fy, vertical / forward / backward motion, roll, a reference pose that is not the
+    identity), six frames each: bit parity where the two image axes and all of R and t matter."""
+    p = pair(SC.W, SC.H, K=SC.K)
+    for k, (img, T) in enumerate(SC.scene(name, 1)):
+        o = p.track(img, T, k == 0)
+        assert k == 0 or p.ref.counts.get(R.OK, 0) >= 30
+    assert (o["idepth_var"] < 0.01).sum() >= 15
 
 
 @pytest.mark.parametrize("tx,steps", [(0.1, 140), (1.0, 256)])
