@@ -13,6 +13,7 @@
 // Tile plan (tile path): per tile a TileDesc + slices of the flat arrays t_vmap / t_eij /
 // t_ew / t_emap / t_srow (see TileDesc).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 namespace flamehip {
@@ -85,10 +86,43 @@ FLAME_HD inline uint32_t slot_row_word(int32_t row_start, int32_t degree) { retu
 // Cost model of a tile for the balance of the partition (both plan builders, integer): a launch / a round lasts as long as its
 // slowest tile -- local edges + 2 x local vertices (r02).  (r05 tried local edges + 2 x UPDATED vertices, what a resident tile's
 // iterate time correlates with best at 50 k: -1 % there, +6...18 % at 20 k / 100 k / 200 k, profiles/r05_cost_model_ab.txt.)
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-inline long long tile_cost(const TileDesc& D) { return (long long)D.e_loc + 2 * (long long)D.n_ext; }
+FLAME_HD inline long long tile_cost(const TileDesc& D) { return (long long)D.e_loc + 2 * (long long)D.n_ext; }
+// Integer cost density of a tile (x 1024): what one own vertex of the tile "costs" a launch.  Integer so that sums of it are
+// exact whatever the summation order (a host loop, device atomics).
+FLAME_HD inline int32_t tile_weight(const TileDesc& D) {
+  const long long w = tile_cost(D) * 1024 / (D.n_own > 1 ? D.n_own : 1);
+  return (int32_t)(w > 1 ? w : 1);
+}
+// Cell of a position in the kCostGrid x kCostGrid cost-density field over the bounding box [mn, mx] of a frame's positions
+// (Plan::wgrid: the next frame's balance weights).  Float arithmetic, so every builder evaluates this one expression.
+constexpr int kCostGrid = 32;
+FLAME_HD inline int cost_grid_cell(const float* mn, const float* mx, float x, float y) {
+  const float fx = (x - mn[0]) / fmaxf(mx[0] - mn[0], 1e-20f);
+  const float fy = (y - mn[1]) / fmaxf(mx[1] - mn[1], 1e-20f);
+  const int ix = (int)(fx * kCostGrid), iy = (int)(fy * kCostGrid);
+  const int cx = ix < 0 ? 0 : (ix > kCostGrid - 1 ? kCostGrid - 1 : ix);
+  const int cy = iy < 0 ? 0 : (iy > kCostGrid - 1 ? kCostGrid - 1 : iy);
+  return cy * kCostGrid + cx;
+}
+// Bits of a 16-bit coordinate spread to the even positions: Morton code = spread(qx) | spread(qy) << 1 (the spatial vertex
+// order inside a tile).
+FLAME_HD inline uint32_t morton_spread16(uint32_t x) {
+  x &= 0xffff; x = (x | (x << 8)) & 0x00ff00ff; x = (x | (x << 4)) & 0x0f0f0f0f;
+  x = (x | (x << 2)) & 0x33333333; x = (x | (x << 1)) & 0x55555555;
+  return x;
+}
+
+// ---- phase D of the tile kernels, as the lane order of a 64-edge block prices it (plan.cpp assign_lanes(), plan_dev.hip
+// assign_lanes_block()) ----
+// ds_read_b128 is served in 4 groups of 16 lanes: {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, and the same of lanes 32-63.
+FLAME_HD inline int lane_read_group(int lane) {
+  const int l = lane & 31;
+  return ((l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28)) ? 0 : 1) + 2 * (lane >> 5);
+}
+// An edge end without an incidence slot (0xffff: its vertex is never updated) stores into the lane's own trash slot.  (The
+// resident tiles' poll lists stage a halo edge through the source's slot, else the target's, else that trash slot: kernels.hip
+// k_poll_lists.)
+FLAME_HD inline uint32_t edge_store_slot(uint32_t slot, int32_t nslots, int lane) { return slot != 0xffffu ? slot : (uint32_t)(nslots + lane); }
 
 // Local edge record halves.
 //   t_eij[e] = {li | lj << 16, slot_src | slot_dst << 16}   (local vertex ids / incidence slots)

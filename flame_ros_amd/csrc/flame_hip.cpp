@@ -971,26 +971,24 @@ static int upload_device_plan(flame_hip_graph* g, const float* pos, const int32_
     return launch_init_state(s, V, g->v_i2o_dev, g->in_pos, g->in_z, g->in_wgt, have_x0 ? g->in_x0 : nullptr, g->A[0],
                              g->B[0], g->pos, E > 0 ? E : 1, g->q[0], g->q[1]);
   };
-  int tile_own = sz.tile_own;
-  int depth = sz.depth;
-  bool fat = sz.fat;
-  bool slot12 = false, fat_cfg = false, fat_s12 = false;
-  bool balanced = false, built = false;
-  int refine_left = 0;
+  PlanAttempts policy(g->opt, sz, V, g->opt.balance != 0);  // (plan.h: the attempt policy of both builders; never a batch or an isolated tile here)
+  bool slot12 = false, fat_cfg = false;
+  bool built = false;
   int ntiles = 0, cfg_nt = 0, cfg_ept = 0, cfg_vpt = 0;
   int64_t lds_max = 0;
   std::vector<TileDesc>& tiles = P.tiles;
   // A frame stream re-uses the previous frame's PARTITION (the tile of every spatial cell) while the
   // frames stay alike: no sorts, no bisection (option "plan_reuse", default on; results are the
   // oracle's bits on any partition).  One try; a frame it does not suit is bisected as usual.
-  bool try_reuse = g->plan_reuse && g->opt.balance && g->planner.map_usable(V, depth) &&
+  bool try_reuse = g->plan_reuse && g->opt.balance && g->planner.map_usable(V, policy.depth()) &&
                    g->opt.tile_own == g->reuse_tile_own_opt;
   if (try_reuse && g->reuse_skip > 0) { --g->reuse_skip; try_reuse = false; }  // back-off after rejections
   g->plan_reused = false;
-  const int max_attempts = 10 + kBalanceRefinePasses + (sz.fat ? 7 * (2 + kBalanceRefinePasses) : 0);  // (plan.cpp)
+  const int max_attempts = policy.max_attempts() + 1;  // (+ 1: the partition-reuse try)
   for (int attempt = 0; attempt < max_attempts && !built; ++attempt) {
     const bool reusing = try_reuse;
     try_reuse = false;
+    const int tile_own = policy.tile_own(), depth = policy.depth();
     ntiles = reusing ? g->planner.map_tiles() : (V + tile_own - 1) / tile_own;
     if (ntiles < 2) return 0;
     // every retry halves tile_own: the tile count may have outgrown the builder's segment tables
@@ -998,10 +996,10 @@ static int upload_device_plan(flame_hip_graph* g, const float* pos, const int32_
     if (attempt > 0 && !reusing && !DevPlanner::eligible(g->opt, V, E, T, tile_own, depth, false, g->opt.lds_bytes)) return 0;
     if (reusing) {
       g->planner.reuse_partition();
-    } else if (!balanced) {
+    } else if (!policy.balanced()) {
       if (g->opt.balance && ntiles >= 16 && g->planner.grid_tiles() == ntiles) {
         g->planner.set_weights_from_grid();  // a frame stream balances in ONE pass
-        balanced = true;
+        policy.start_balanced();
       } else {
         g->planner.set_weights_none();
       }
@@ -1018,7 +1016,7 @@ static int upload_device_plan(flame_hip_graph* g, const float* pos, const int32_
     if (index_error) return FLAME_HIP_ERR_ARG;
     const bool tiles_valid = ok;  // every tile was built (it may still be too large for LDS / a kernel config)
     if (ok) {
-      const TileFit fit = tile_fit(g->opt, fat, tiles, fat_s12);  // (LDS, kernel configuration, 12-byte slots: plan.cpp)
+      const TileFit fit = tile_fit(g->opt, policy.fat(), tiles, policy.fat_s12());  // (LDS, kernel configuration, 12-byte slots: plan.cpp)
       ok = fit.ok;
       lds_max = fit.lds_bytes; slot12 = fit.slot12; fat_cfg = fit.fat;
       cfg_nt = fit.nt; cfg_ept = fit.ept; cfg_vpt = fit.vpt;
@@ -1039,41 +1037,28 @@ static int upload_device_plan(flame_hip_graph* g, const float* pos, const int32_
       g->planner.drop_map();  // scene change / does not fit: exact bisection from here on
       g->reuse_backoff = std::min(16, std::max(1, 2 * g->reuse_backoff));  // a wasted attempt costs a build:
       g->reuse_skip = g->reuse_backoff;                                     // try again 1, 2, 4 ... 16 frames later
-      balanced = false;
       continue;
     }
-    // Only the LARGEST tile decides whether a partition fits, and before the cost balance that is a
-    // border tile (long hull edges => a halo up to 1.5 x the median): balance first, shrink only
-    // if the balanced partition does not fit either.
-    if (!ok && tiles_valid && g->opt.balance && !balanced && ntiles >= 16) {
-      balanced = true;
-      refine_left = kBalanceRefinePasses;
-      HIPCHK(g->planner.weights_from_tiles(s, V, A));
-      continue;
+    switch (policy.after(tiles_valid, ok, ntiles)) {
+      case PlanAttempts::kAccept:
+        built = true;
+        break;
+      case PlanAttempts::kWeightsFromTiles:  // cost-weighted pass, same tile count
+        HIPCHK(g->planner.weights_from_tiles(s, V, A));
+        break;
+      case PlanAttempts::kScaleWeights: {
+        long long total = 0;
+        for (const TileDesc& D : tiles) total += tile_cost(D);
+        HIPCHK(g->planner.weights_scale_by_tiles(s, V, ntiles, total, A));
+        break;
+      }
+      case PlanAttempts::kNewGeometry:  // did not fit: other sizes, plain bisection again
+      case PlanAttempts::kSingleNoFit:  // (not on this path: DevPlanner::eligible() declines an isolated tile)
+        g->planner.drop_grid();
+        break;
     }
-    if (ok && g->opt.balance && !balanced && ntiles >= 16) {
-      balanced = true;
-      refine_left = kBalanceRefinePasses;
-      HIPCHK(g->planner.weights_from_tiles(s, V, A));  // second, cost-weighted pass, same tile count
-      continue;
-    }
-    if (ok && balanced && refine_left > 0 && ntiles >= 16) {  // refinement passes (plan.cpp)
-      --refine_left;
-      long long total = 0;
-      for (const TileDesc& D : tiles) total += tile_cost(D);
-      HIPCHK(g->planner.weights_scale_by_tiles(s, V, ntiles, total, A));
-      continue;
-    }
-    if (ok) { built = true; break; }
-    // did not fit: smaller tiles, plain bisection again
-    g->planner.drop_grid();
-    balanced = false;
-    refine_left = 0;
-    if (fat && fat_next_attempt(g->opt, sz, &depth, &fat_s12)) {}  // fat tiles: shallower / 12-byte slots first (plan.cpp)
-    else if (fat) { fat = false; tile_own = sz.fallback_own; depth = sz.fallback_depth; }
-    else if (regular_next_attempt(g->opt, sz, V, &tile_own, &depth)) {}  // (plan.cpp)
-    else tile_own = std::max(16, tile_own / 2);
   }
+  const int depth = policy.depth();
   if (!built) return 0;
   lap("plan build");
   {  // how even the tiles are (a launch lasts as long as its slowest tile): max / mean of the cost model

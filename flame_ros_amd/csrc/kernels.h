@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "tile_cfgs.h"  // which configurations exist: tile_config_exists() / tile_persist_exists() / tile_slot12_exists()
 
 namespace flamehip {
 
@@ -36,8 +37,6 @@ hipError_t launch_primal(hipStream_t s, int32_t V, const int32_t* grow, const in
 // ---- tile path: `iters` PD iterations per launch on LDS-resident subdomains ----
 hipError_t launch_tile(hipStream_t s, int nt, int ept, int vpt, size_t lds_bytes,
                        const TileArgs& a);
-bool tile_config_exists(int nt, int ept, int vpt);
-bool tile_slot12_exists(int nt, int ept, int vpt);  // ... with 12-byte incidence slots (resident or by launches)
 // one-time per configuration: opt in to > 48 KiB of dynamic LDS (not capturable in a hipGraph)
 hipError_t prepare_tile(int nt, int ept, int vpt, size_t lds_bytes, bool slot12 = false);
 // resident tiles (ONE launch for the whole solve; graphs of 2 .. kPersistMaxTiles tiles, at most one per CU: every
@@ -68,7 +67,6 @@ struct PersistBufs {
   int32_t timeout_ticks = 0;  // 10 ns ticks a poll may wait (0 = 4 ms)
   int32_t one_xcd = 0;     // r06 one-XCD mode (kernels.hip PersistArgs::one_xcd; graphs of <= 32 tiles): hA / hB / hq are ordinary memory then
 };
-bool tile_persist_exists(int nt, int ept, int vpt);
 hipError_t launch_poll_lists(hipStream_t s, int32_t ntiles, const TileDesc* tiles, const int32_t* t_vmap, const int32_t* t_emap,
                              const uint2* t_eij, uint2* poll_v, uint2* poll_e, int32_t* poll_ne, bool sorted,
                              int32_t* need_v = nullptr, int32_t* need_e = nullptr);

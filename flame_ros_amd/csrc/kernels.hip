@@ -1868,45 +1868,27 @@ hipError_t launch_primal(hipStream_t s, int32_t V, const int32_t* grow, const in
   return hipGetLastError();
 }
 
-#define FLAME_TILE_CFGS(X)                                                             \
-  X(256, 2, 1) X(256, 3, 1) X(256, 4, 1) X(256, 6, 1) X(256, 4, 2) X(256, 6, 2)         \
-  X(512, 2, 1) X(512, 3, 1) X(512, 4, 1) X(512, 6, 1) X(512, 4, 2) X(512, 6, 2)         \
-  X(1024, 2, 1) X(1024, 3, 1) X(1024, 4, 1) X(1024, 6, 1) X(1024, 4, 2) X(1024, 6, 2)
-
-// 12-byte incidence slots (fat tiles, SlotMem<true>): the configurations a one-tile-per-CU partition of a graph beyond
-// 256 x 196 vertices gets
-#define FLAME_S12_CFGS(X) X(1024, 2, 1) X(1024, 3, 1)
-
-bool tile_config_exists(int nt, int ept, int vpt) {
-#define X(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return true;
-  FLAME_TILE_CFGS(X)
-#undef X
-  return false;
-}
-bool tile_slot12_exists(int nt, int ept, int vpt) {
-#define X(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return true;
-  FLAME_S12_CFGS(X)
-#undef X
-  return false;
+// The (nt, ept, vpt) a plan names, turned into template arguments: f(CfgT<N, Ep, Vp>{}) for the entry of a list of
+// tile_cfgs.h that equals it.  Only the entries of the list that is asked for are instantiated.
+template <int N, int Ep, int Vp> struct CfgT { static constexpr int nt = N, ept = Ep, vpt = Vp; };
+enum class CfgList { kTile, kPersist, kSlot12 };
+template <CfgList L, class F>
+hipError_t dispatch_cfg(int nt, int ept, int vpt, F f) {
+#define FLAME_CFG_CASE(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return f(CfgT<N, Ep, Vp>{});
+  if constexpr (L == CfgList::kTile) { FLAME_TILE_CFGS(FLAME_CFG_CASE) }
+  else if constexpr (L == CfgList::kPersist) { FLAME_PERSIST_CFGS(FLAME_CFG_CASE) }
+  else { FLAME_S12_CFGS(FLAME_CFG_CASE) }
+#undef FLAME_CFG_CASE
+  return hipErrorInvalidConfiguration;
 }
 
 hipError_t launch_tile(hipStream_t s, int nt, int ept, int vpt, size_t lds_bytes,
                        const TileArgs& a) {
   if (a.ntiles <= 0 || a.iters <= 0) return hipSuccess;
-  if (a.slot12) {
-#define X(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return launch_tile_t<N, Ep, Vp, true>(s, lds_bytes, a);
-    FLAME_S12_CFGS(X)
-#undef X
-    return hipErrorInvalidConfiguration;
-  }
-#define X(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return launch_tile_t<N, Ep, Vp>(s, lds_bytes, a);
-  FLAME_TILE_CFGS(X)
-#undef X
-  return hipErrorInvalidConfiguration;
+  if (a.slot12)
+    return dispatch_cfg<CfgList::kSlot12>(nt, ept, vpt, [&](auto c) { return launch_tile_t<c.nt, c.ept, c.vpt, true>(s, lds_bytes, a); });
+  return dispatch_cfg<CfgList::kTile>(nt, ept, vpt, [&](auto c) { return launch_tile_t<c.nt, c.ept, c.vpt>(s, lds_bytes, a); });
 }
-
-// persistent variant: the configurations small graphs get
-#define FLAME_PERSIST_CFGS(X) X(256, 2, 1) X(256, 3, 1) X(512, 2, 1) X(512, 3, 1) X(1024, 2, 1) X(1024, 3, 1)
 
 // ---- the resident tiles' address-sorted poll lists (PersistArgs::poll_*): per tile, its halo vertices and its halo edges in
 // ascending GLOBAL id.  Derived from the finished tile arrays whoever made them (host builder, device builder, one-launch
@@ -1961,6 +1943,8 @@ __global__ __launch_bounds__(kPollThreads) void k_poll_lists(const TileDesc* __r
       const int32_t eid = t_emap[D.emap_off + le];
       const bool owned = (uint32_t)(eid - D.estart) < (uint32_t)D.e_own;
       const uint32_t sl = t_eij[D.erec_off + le].y, ss = sl & 0xffffu, sd = sl >> 16;
+      // the staged slot: the source's, else the target's, else the lane's trash slot -- common.h edge_store_slot() is the shared
+      // statement of the last; spelled out here and below, since a shared helper costs this kernel 7 VGPRs (17 -> 24, unsorted variant)
       const uint32_t slot = ss != 0xffffu ? ss : (sd != 0xffffu ? sd : (uint32_t)(D.nslots + (le & 63)));
       poll_e[D.emap_off + le] = make_uint2(owned ? 0xffffffffu : (uint32_t)eid, slot);
     }
@@ -2022,13 +2006,6 @@ hipError_t launch_poll_lists(hipStream_t s, int32_t ntiles, const TileDesc* tile
 bool tile_torn_check_build() { return FLAME_TORN_CHECK != 0; }
 bool tile_stall_hook_build() { return FLAME_PERSIST_STALL_HOOK != 0; }
 
-bool tile_persist_exists(int nt, int ept, int vpt) {
-#define X(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return true;
-  FLAME_PERSIST_CFGS(X)
-#undef X
-  return false;
-}
-
 template <int NT, int EPT, int VPT, bool S12 = false, bool FAT = false>
 hipError_t launch_tile_persist_t(hipStream_t s, size_t lds, const TileArgs& a, const PersistArgs& pa) {
   if (lds > 48 * 1024) {
@@ -2052,30 +2029,18 @@ hipError_t launch_tile_persist(hipStream_t s, int nt, int ept, int vpt, size_t l
   for (int b = 0; b < 2; ++b) { pa.hA[b] = x.hA[b]; pa.hB[b] = x.hB[b]; pa.hq[b] = x.hq[b]; }
   pa.poll_v = x.poll_v; pa.poll_e = x.poll_e; pa.poll_ne = x.poll_ne;
   pa.need_v = (x.need_valid && a.fat) ? x.need_v : nullptr; pa.need_e = (x.need_valid && a.fat) ? x.need_e : nullptr;
-  if (a.slot12 || a.fat) {  // the fat variants: 1 024 threads, 2 or 3 edges per thread, either slot layout
-#define X(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return a.slot12 ? launch_tile_persist_t<N, Ep, Vp, true, true>(s, lds_bytes + x.stage_bytes, a, pa) \
-                                                                            : launch_tile_persist_t<N, Ep, Vp, false, true>(s, lds_bytes + x.stage_bytes, a, pa);
-    FLAME_S12_CFGS(X)
-#undef X
-    return hipErrorInvalidConfiguration;
-  }
-#define X(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return launch_tile_persist_t<N, Ep, Vp>(s, lds_bytes + x.stage_bytes, a, pa);
-  FLAME_PERSIST_CFGS(X)
-#undef X
-  return hipErrorInvalidConfiguration;
+  const size_t lds = lds_bytes + x.stage_bytes;
+  if (a.slot12 || a.fat)  // the fat variants: 1 024 threads, 2 or 3 edges per thread, either slot layout
+    return dispatch_cfg<CfgList::kSlot12>(nt, ept, vpt, [&](auto c) {
+      return a.slot12 ? launch_tile_persist_t<c.nt, c.ept, c.vpt, true, true>(s, lds, a, pa)
+                      : launch_tile_persist_t<c.nt, c.ept, c.vpt, false, true>(s, lds, a, pa);
+    });
+  return dispatch_cfg<CfgList::kPersist>(nt, ept, vpt, [&](auto c) { return launch_tile_persist_t<c.nt, c.ept, c.vpt>(s, lds, a, pa); });
 }
 
 hipError_t prepare_tile(int nt, int ept, int vpt, size_t lds_bytes, bool slot12) {
-  if (slot12) {
-#define X(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return prepare_tile_t<N, Ep, Vp, true>(lds_bytes);
-    FLAME_S12_CFGS(X)
-#undef X
-    return hipErrorInvalidConfiguration;
-  }
-#define X(N, Ep, Vp) if (nt == N && ept == Ep && vpt == Vp) return prepare_tile_t<N, Ep, Vp>(lds_bytes);
-  FLAME_TILE_CFGS(X)
-#undef X
-  return hipErrorInvalidConfiguration;
+  if (slot12) return dispatch_cfg<CfgList::kSlot12>(nt, ept, vpt, [&](auto c) { return prepare_tile_t<c.nt, c.ept, c.vpt, true>(lds_bytes); });
+  return dispatch_cfg<CfgList::kTile>(nt, ept, vpt, [&](auto c) { return prepare_tile_t<c.nt, c.ept, c.vpt>(lds_bytes); });
 }
 
 int costs_num_blocks(int32_t, int32_t) { return kCostBlocks; }

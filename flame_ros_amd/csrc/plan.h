@@ -99,7 +99,7 @@ struct Plan {
   std::vector<uint32_t> b_code;
   // cost-density field of the last balanced partition on a coarse pixel grid: a handle that is
   // re-uploaded every frame balances the next frame in ONE weighted pass instead of two
-  static constexpr int kGrid = 32;
+  static constexpr int kGrid = kCostGrid;
   std::vector<int32_t> wgrid;  // kGrid * kGrid integer cost densities (x 1024), empty = none yet
   float wgrid_mn[2] = {0.f, 0.f}, wgrid_mx[2] = {1.f, 1.f};
   int32_t wgrid_tiles = 0;   // tile count the field was built for
@@ -135,20 +135,55 @@ struct TileFit {
 // e_max / ext_max / upd_max / hv_max: the largest tile's local edges, local vertices, updated vertices, halo vertices;
 // lds16 / lds12: max over the tiles of tile_lds_bytes() (+ the resident tiles' staging area when `resident`)
 TileFit tile_fit(const PlanOptions& opt, bool fat, const std::vector<TileDesc>& tiles, bool allow_slot12 = true);
-// what a fat partition that did not fit tries next (both plan builders): false = nothing left, take the fallback
-bool fat_next_attempt(const PlanOptions& opt, const PlanSizing& sz, int* depth, bool* allow_slot12);
-// r06, regular tiles sized for ONE resident launch (automatic sizes, at most one tile per CU) that do not fit -- LDS with the
-// resident launch's staging area, a kernel configuration that has a resident variant --: halving the tiles would put more
-// tiles than CUs on the chip and the solve on launches (4 x slower), so the same tiles are first tried one halo level
-// shallower, down to depth 2 (the subdomains of a partitioned 200 k graph: 46-48 k local vertices with ragged halo bands,
-// half of them fell back to 511-515 tiles or to four edges per thread, profiles/r06_partition_parts_resident.txt).  Returns
-// true when *depth was lowered; else the caller halves *tile_own (and this call has restored the automatic depth).
-bool regular_next_attempt(const PlanOptions& opt, const PlanSizing& sz, int32_t V, int* tile_own, int* depth);
+// The attempt policy of BOTH plan builders (build_plan() on the host; flame_hip.cpp upload_device_plan() driving plan_dev.hip on
+// the device): which partition to build next.  A builder builds one attempt from tile_own() / depth(), prices it with
+// tile_fit(opt, fat(), tiles, fat_s12()) and does what after() returns; the body of each action is the builder's own.
+//   Balance: only the LARGEST tile decides whether a partition fits, and before the cost balance that is a border tile (long hull
+// edges => a halo up to 1.5 x the median).  So the first valid partition of >= 16 tiles is rebuilt on cost weights taken from its
+// tiles whether it fits or not, then refined kBalanceRefinePasses times while it fits; a builder that already has weights (the
+// previous frame's cost grid) says start_balanced() and gets no refinement.
+//   A partition that does not fit after that: an isolated tile becomes the automatic halo'd partition (or kSingleNoFit);
+// fat tiles go shallower, then to 12-byte slots, then to the fallback sizes; regular tiles sized for one resident launch go
+// shallower; anything else is halved.
+class PlanAttempts {
+ public:
+  enum Action {
+    kAccept,            // the plan is final
+    kWeightsFromTiles,  // every vertex takes the tile_weight() of its tile; rebuild (same tile count)
+    kScaleWeights,      // refinement: every vertex weight x its tile's cost / the mean tile cost; rebuild (same tile count)
+    kNewGeometry,       // did not fit: drop the weights and the cost grid, rebuild from tile_own() / depth() / ...
+    kSingleNoFit,       // the isolated tile does not fit and the caller asked to be told (PlanOptions::single_only)
+  };
+  // balance: whether cost balancing applies to this graph at all (the option; never a batch).  An isolated tile is excluded here.
+  PlanAttempts(const PlanOptions& opt, const PlanSizing& sz, int32_t V, bool balance);
+  // Builds a builder may spend before it gives up on tiles (halving never ends by itself).  A batch is built once; fat tiles: every
+  // halo depth that does not fit costs a balance sequence of its own before the next one is tried.
+  int max_attempts() const {
+    return !opt_.batch_voff.empty() ? 1 : 9 + kBalanceRefinePasses + (sz_.fat ? 7 * (2 + kBalanceRefinePasses) : 0);
+  }
+  void start_balanced() { balanced_ = true; }
+  Action after(bool tiles_valid, bool fit_ok, int ntiles);
+  int tile_own() const { return tile_own_; }
+  int depth() const { return depth_; }
+  bool single() const { return single_; }
+  bool fat() const { return fat_; }
+  bool fat_s12() const { return fat_s12_; }  // fat tiles: the attempts with 16-byte slots come first
+  bool balanced() const { return balanced_; }
+
+ private:
+  bool fat_next();      // false = nothing left, take the fallback
+  bool regular_next();  // true when depth_ was lowered; else the caller halves tile_own_
+  const PlanOptions& opt_;
+  const PlanSizing sz_;
+  const int32_t V_;
+  const bool balance_;
+  int tile_own_, depth_;
+  bool single_, fat_, fat_s12_ = false, balanced_ = false;
+  int refine_left_ = 0;
+};
 // the tiles of a partition are meant to be resident: the caller solves that way and there is at most one tile per CU
 inline bool wants_resident(const PlanOptions& opt, size_t ntiles) { return opt.resident && ntiles >= 2 && (int64_t)ntiles <= std::min(256, opt.num_cus); }
 PlanSizing plan_sizing(const PlanOptions& opt, int32_t V, int32_t E);
-// smallest instantiated kernel configuration that holds e_max local edges / upd_max local vertices
-bool pick_tile_config(int want_nt, int e_max, int upd_max, int* nt, int* ept, int* vpt);
 
 // Builds the plan.  Returns 0 or a FLAME_HIP_ERR_* code (bad indices).
 int build_plan(const PlanOptions& opt, int32_t V, int32_t E, int32_t T, const float* pos,

@@ -66,12 +66,6 @@ __device__ __forceinline__ uint32_t ord_f(float f) {  // order-preserving float 
 __device__ __forceinline__ float unord_f(uint32_t u) {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
-__device__ __forceinline__ uint32_t spread16(uint32_t x) {
-  x &= 0xffff; x = (x | (x << 8)) & 0x00ff00ff; x = (x | (x << 4)) & 0x0f0f0f0f;
-  x = (x | (x << 2)) & 0x33333333; x = (x | (x << 1)) & 0x55555555;
-  return x;
-}
-
 template <int NTB, class T>
 __device__ void bitonic_sort(T* a, int m) {  // m a power of two, ascending
   const int tid = threadIdx.x;
@@ -777,7 +771,7 @@ __global__ __launch_bounds__(256) void k_tile_order(int32_t V, int32_t ntiles, c
       // the frame it was made from)
       const uint32_t qx = (uint32_t)(65535.0f * (fminf(fmaxf(q.x, mnx), mxx) - mnx) / fmaxf(mxx - mnx, 1e-20f));
       const uint32_t qy = (uint32_t)(65535.0f * (fminf(fmaxf(q.y, mny), mxy) - mny) / fmaxf(mxy - mny, 1e-20f));
-      k = ((uint64_t)(spread16(qx) | (spread16(qy) << 1)) << 32) | (uint32_t)v;
+      k = ((uint64_t)(morton_spread16(qx) | (morton_spread16(qy) << 1)) << 32) | (uint32_t)v;
     }
     keys[p] = k;
   }
@@ -1237,8 +1231,7 @@ __global__ __launch_bounds__(kSegCap) void k_tile_offsets(int ntiles, int32_t* m
 template <bool S12>
 __device__ __forceinline__ void assign_lanes_block(int lane, int b0, int e_loc, int32_t eoff, int32_t nslots,
                                                    uint2* t_eij, float4* t_ew, int32_t* t_emap) {
-  const int hl = lane & 31;
-  const int rg = ((hl < 4 || (hl >= 12 && hl < 16) || (hl >= 20 && hl < 28)) ? 0 : 1) + 2 * (lane >> 5);
+  const int rg = lane_read_group(lane);
   const int wg = lane >> 3;
   const int c = min(64, e_loc - b0);
   const int src_i = eoff + b0 + min(lane, c - 1);
@@ -1255,9 +1248,7 @@ __device__ __forceinline__ void assign_lanes_block(int lane, int b0, int e_loc, 
     const uint32_t ey = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, k);
     const int32_t li = (int32_t)(ex & 0xffffu), lj = (int32_t)(ex >> 16);
     const uint32_t ss = ey & 0xffffu, sd = ey >> 16;
-    // a lane without a slot stores into its own trash slot (nslots + lane)
-    const uint32_t s1 = ss != 0xffffu ? ss : (uint32_t)(nslots + lane);
-    const uint32_t s2 = sd != 0xffffu ? sd : (uint32_t)(nslots + lane);
+    const uint32_t s1 = edge_store_slot(ss, nslots, lane), s2 = edge_store_slot(sd, nslots, lane);
     const int32_t fs = __shfl(T_rs, rg * 16 + (li & 15), 64), ft = __shfl(T_rt, rg * 16 + (lj & 15), 64);
     int cost;
     if (S12) {
@@ -1273,11 +1264,9 @@ __device__ __forceinline__ void assign_lanes_block(int lane, int b0, int e_loc, 
       const unsigned long long m = __ballot(!used && cost == cc);
       if (m) best = (int)__builtin_ctzll(m);
     }
-    const int hb = best & 31;
-    const int rgb = ((hb < 4 || (hb >= 12 && hb < 16) || (hb >= 20 && hb < 28)) ? 0 : 1) + 2 * (best >> 5);
+    const int rgb = lane_read_group(best);
     const int wgb = best >> 3;
-    const uint32_t s1b = ss != 0xffffu ? ss : (uint32_t)(nslots + best);
-    const uint32_t s2b = sd != 0xffffu ? sd : (uint32_t)(nslots + best);
+    const uint32_t s1b = edge_store_slot(ss, nslots, best), s2b = edge_store_slot(sd, nslots, best);
     if (lane == best) { used = true; got = k; }
     if (lane == rgb * 16 + (li & 15) && T_rs == 0) T_rs = li + 1;
     if (lane == rgb * 16 + (lj & 15) && T_rt == 0) T_rt = lj + 1;
@@ -1639,19 +1628,13 @@ __global__ __launch_bounds__(256) void k_publish(const int32_t* __restrict__ fla
 
 // ------------------------------------------------------------------------------------------
 // Cost weights: from the tiles of the previous pass, or from the cost-density grid of the
-// previous frame (plan.cpp: tile_weight(), Plan::wgrid).  All integer.
+// previous frame (common.h: tile_weight(), cost_grid_cell(); Plan::wgrid).  All integer.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int32_t tile_weight_dev(const TileDesc& D) {
-  const long long cost = tile_cost(D);
-  const long long w = cost * 1024 / max(D.n_own, 1);
-  return (int32_t)max(1ll, w);
-}
-
 __global__ __launch_bounds__(256) void k_weights_from_tiles(int32_t V, const int32_t* __restrict__ v_i2o,
                                                             const int32_t* __restrict__ tile_of_int,
                                                             const TileDesc* __restrict__ tiles, int32_t* w_int) {
   const int32_t k = blockIdx.x * 256 + threadIdx.x;
-  if (k < V) w_int[v_i2o[k]] = tile_weight_dev(tiles[tile_of_int[k]]);
+  if (k < V) w_int[v_i2o[k]] = tile_weight(tiles[tile_of_int[k]]);
 }
 
 // refinement pass: w_v <- w_v * cost(tile of v) * ntiles / total cost (plan.cpp, "refine weights")
@@ -1666,14 +1649,6 @@ __global__ __launch_bounds__(256) void k_weights_scale(int32_t V, const int32_t*
   const int32_t v = v_i2o[k];
   const long long w = (long long)w_int[v] * cost * ntiles / max(total, 1ll);
   w_int[v] = (int32_t)min(1ll << 28, max(1ll, w));
-}
-
-__device__ __forceinline__ int grid_cell_dev(const float* b, float2 q) {
-  const float fx = (q.x - b[0]) / fmaxf(b[2] - b[0], 1e-20f);
-  const float fy = (q.y - b[1]) / fmaxf(b[3] - b[1], 1e-20f);
-  const int cx = max(0, min(Plan::kGrid - 1, (int)(fx * Plan::kGrid)));
-  const int cy = max(0, min(Plan::kGrid - 1, (int)(fy * Plan::kGrid)));
-  return cy * Plan::kGrid + cx;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1778,7 +1753,9 @@ __global__ __launch_bounds__(256) void k_weights_from_grid(int32_t V, const floa
                                                            const float* __restrict__ bounds,
                                                            const int32_t* __restrict__ grid_w, int32_t* w_int) {
   const int32_t v = blockIdx.x * 256 + threadIdx.x;
-  if (v < V) w_int[v] = grid_w[grid_cell_dev(bounds, pos[v])];
+  if (v >= V) return;
+  const float2 q = pos[v];
+  w_int[v] = grid_w[cost_grid_cell(bounds, bounds + 2, q.x, q.y)];
 }
 
 __global__ __launch_bounds__(256) void k_grid_accum(int32_t V, const float2* __restrict__ pos,
@@ -1796,8 +1773,8 @@ __global__ __launch_bounds__(256) void k_grid_accum(int32_t V, const float2* __r
   const int32_t k = blockIdx.x * 256 + threadIdx.x;
   if (k < V) {
     const float2 q = pos[v_i2o[k]];
-    const int c = grid_cell_dev(bounds, q);
-    atomicAdd(&s_sum[c], (unsigned long long)tile_weight_dev(tiles[tile_of_int[k]]));
+    const int c = cost_grid_cell(bounds, bounds + 2, q.x, q.y);
+    atomicAdd(&s_sum[c], (unsigned long long)tile_weight(tiles[tile_of_int[k]]));
     atomicAdd(&s_cnt[c], 1);
     if (pyr) {  // the tile map the next frame's partition is read from (partition reuse)
       const int32_t tv = tile_of_int[k] + 1;
@@ -2259,7 +2236,7 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
           const float2 q = s_pos[v];
           const uint32_t qx = (uint32_t)(65535.0f * (fminf(fmaxf(q.x, mnx), mxx) - mnx) / fmaxf(mxx - mnx, 1e-20f));
           const uint32_t qy = (uint32_t)(65535.0f * (fminf(fmaxf(q.y, mny), mxy) - mny) / fmaxf(mxy - mny, 1e-20f));
-          k = ((uint64_t)(spread16(qx) | (spread16(qy) << 1)) << 32) | (uint32_t)v;
+          k = ((uint64_t)(morton_spread16(qx) | (morton_spread16(qy) << 1)) << 32) | (uint32_t)v;
         }
         mine[h] = k;
         keys[p] = k;

@@ -346,6 +346,33 @@ def test_fat_tile_sizing():
             assert r1.info("num_tiles") > 256 and r1.info("tile_slot12") == 0
 
 
+ATTEMPTS = [  # options -> (num_tiles, threads, ept, vpt, tile_depth, tile_lds_bytes), or None: no tile plan fits
+    ({}, (209, 512, 2, 1, 5, 68112)),
+    (dict(lds_bytes=65536), (209, 512, 2, 1, 4, 44848)),   # the halo one ...
+    (dict(lds_bytes=49152), (209, 256, 2, 1, 3, 32368)),   # ... two ...
+    (dict(lds_bytes=32768), (209, 256, 2, 1, 2, 17888)),   # ... three levels shallower, the tiles as they were
+    (dict(tile_own=64, tile_depth=2, lds_bytes=24000), (157, 256, 2, 1, 2, 18976)),  # forced sizes: halved once
+    (dict(lds_bytes=16384), None),
+]
+
+
+@pytest.mark.parametrize("opts,want", ATTEMPTS)
+def test_attempt_policy_branches(opts, want):
+    """What a partition that does not fit tries next (PlanAttempts, the policy of both plan builders): tiles sized for one
+    resident launch keep their size and take a shallower halo, down to depth 2; forced sizes are halved; when nothing fits
+    the global path remains.  A small LDS forces the branches on a 5 k-vertex graph (the device builder declines such an
+    LDS size, so these cases stand for it too; the fat branches: test_fat_tile_sizing)."""
+    g = graphgen.named("5k")[0]
+    assert (g.V, g.E) == (5000, 14978)
+    r = GraphRegularizer(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, tris=g.tris, device=-1, **opts)
+    if want is None:
+        assert r.info("num_tiles") == 0 and r.info("path") == lib.PATH_GLOBAL
+        return
+    got = tuple(r.info(k) for k in ("num_tiles", "tile_threads", "tile_ept", "tile_vpt", "tile_depth", "tile_lds_bytes"))
+    assert got == want and r.info("path") == lib.PATH_TILE
+    assert r.info("tile_lds_bytes") <= r.info("lds_bytes")
+
+
 def test_one_xcd_sizing():
     """r06: a resident graph of 770 .. 1 280 vertices takes 32 tiles (an XCD has 32 CUs: the tiles hand over through its L2,
     option "one_xcd"); below, the 24-vertex floor already gives at most 32; above, and with the option off or without resident

@@ -1,5 +1,5 @@
 """r06: the parts of the 200 k graph cut 8-way on one rank -- local size, tile plan, resident launches (why half of them were
-not resident before regular_next_attempt(): 511-515 tiles, four edges per thread, LDS + staging over the limit)."""
+not resident before the shallower-halo step of PlanAttempts: 511-515 tiles, four edges per thread, LDS + staging over the limit)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from flame_ros_amd import graphgen, partition
