@@ -28,6 +28,7 @@
 #include "kernels.h"
 #include "plan.h"
 #include "plan_dev.h"
+#include "predict.h"
 #include "sync.h"
 
 using namespace flamehip;
@@ -332,6 +333,17 @@ struct flame_hip_graph {
   int raster_filtered = -1;
   flame_hip_tri_params raster_tp;
   float raster_kinv[9];
+  // prediction stage (flame_hip_predict, predict.h): scratch sized like the dense raster's and kept across frames
+  bool tri_stage_run = false;    // a triangle stage has written tri_valid since the last upload
+  bool is_batch = false;         // the handle holds a batch of graphs (flame_hip_graph_upload_batch)
+  int64_t pg_pixels = 0;         // W x H of the key map the last flame_hip_predict made (0 = none)
+  unsigned long long* pg_key = nullptr;
+  float4* pg_proj = nullptr;
+  float2* pg_pix = nullptr;
+  float* pg_pred = nullptr;
+  float* pg_map = nullptr;
+  hipEvent_t pg_ev0 = nullptr, pg_ev1 = nullptr;
+  double predict_us = 0.0, predict_device_us = 0.0;
   // graph filter scratch (row a9)
   float* filter_tmp = nullptr;
   // mesh output (row f1)
@@ -497,7 +509,7 @@ struct flame_hip_graph {
 
 extern "C" {
 
-int flame_hip_version(void) { return 403; }  // (403: the feature front end, flame_hip_frontend_*; 402, r06: halo view, peer transport, local communicator, handle options instead of environment switches)
+int flame_hip_version(void) { return 404; }  // (404: the prediction stage, flame_hip_predict / _predict_map; 403: the feature front end, flame_hip_frontend_*; 402, r06: halo view, peer transport, local communicator, handle options instead of environment switches)
 
 const char* flame_hip_strerror(int code) {
   switch (code) {
@@ -568,6 +580,8 @@ void flame_hip_graph_destroy(flame_hip_graph* g) {
     if (g->ev1) (void)hipEventDestroy(g->ev1);
     if (g->ev_in) (void)hipEventDestroy(g->ev_in);
     if (g->ev_state) (void)hipEventDestroy(g->ev_state);
+    if (g->pg_ev0) (void)hipEventDestroy(g->pg_ev0);
+    if (g->pg_ev1) (void)hipEventDestroy(g->pg_ev1);
     if (g->stream_in) { (void)hipStreamSynchronize(g->stream_in); (void)hipStreamDestroy(g->stream_in); }
     if (g->stream) (void)hipStreamDestroy(g->stream);
   }
@@ -801,6 +815,9 @@ int flame_hip_get_info(const flame_hip_graph* g, const char* key, int64_t* value
   else if (k == "delaunay_hull") *value = g->dt.last_hull;  // flame_hip_delaunay: boundary vertices / live points / host microseconds of the last call
   else if (k == "delaunay_live") *value = g->dt.last_live;
   else if (k == "delaunay_us") *value = (int64_t)(g->dt.last_ms * 1000.0f);
+  else if (k == "predict_us") *value = (int64_t)(g->predict_us + 0.5);  // flame_hip_predict: host time of the last call / HIP events around its device work
+  else if (k == "predict_device_us") *value = (int64_t)(g->predict_device_us + 0.5);
+  else if (k == "predict_pixels") *value = g->pg_pixels;  // W x H of the map flame_hip_predict_map hands out (0 = none yet)
   else if (k == "lds_bytes") *value = g->opt.lds_bytes;
   else if (k == "num_cus") *value = g->num_cus;
   else if (k == "clock_khz") {  // peak engine clock of the handle's device (timeline cycles -> time)
@@ -823,6 +840,7 @@ int flame_hip_graph_upload_batch(flame_hip_graph* g, int32_t num_graphs, const i
   int rc = flame_hip_graph_upload(g, pos, edges, alpha, beta, z, wgt, x0, tris);
   g->opt.path = saved_path;
   g->opt.batch_voff.clear();
+  if (rc == 0) g->is_batch = true;
   return rc;
 }
 
@@ -1302,6 +1320,8 @@ static int finish_upload(flame_hip_graph* g) {
   g->uploaded = true;
   g->timed = false;
   g->state_scale = 1.0f;
+  g->tri_stage_run = false;  // (tri_valid belongs to the graph before)
+  g->is_batch = false;
   HIPCHK(mark_state(g));
   return 0;
 }
@@ -2182,6 +2202,7 @@ int flame_hip_triangles(flame_hip_graph* g, const float Kinv[9], const flame_hip
   fill_tri_params(Kinv, tp, &d);
   HIPCHK(launch_triangles(g->stream, V, T, g->pos, g->A[g->cur], g->tris, g->trow, g->tinc, d,
                           g->tri_normals, g->tri_valid, g->vtx_normals));
+  g->tri_stage_run = true;
   g->raster_serial = 0;  // tri_valid / vtx_normals were rewritten (maybe with other filter parameters)
   HIPCHK(hipStreamSynchronize(g->stream));
   if (vtx_normals && V > 0) {
@@ -2242,6 +2263,7 @@ static int ensure_raster(flame_hip_graph* g, const float Kinv[9], const flame_hi
   TriParamsDev d;
   fill_tri_params(Kinv, tp, &d);
   hipStream_t s = g->stream;
+  g->tri_stage_run = true;  // (both branches below run the triangle stage)
   if (!cached && V > 0 && T > 0 && npix > 0) {  // everything is due: three launches instead of five or six
     HIPCHK(launch_frame_stage(s, V, g->E, T, tp->width, tp->height, g->pos, g->A[g->cur], g->B[g->cur], g->eij, g->ew, g->tris,
                               g->trow, g->tinc, d, g->tri_normals, g->tri_valid, g->vtx_normals, fo, cost_lambda,
@@ -2347,6 +2369,7 @@ int flame_hip_frame_results(flame_hip_graph* g, const flame_hip_params* p, float
       fill_tri_params(Kinv, tp, &d);
       HIPCHK(launch_triangles(s, V, T, g->pos, g->A[g->cur], g->tris, g->trow, g->tinc, d, g->tri_normals,
                               g->tri_valid, g->vtx_normals, &fo));
+      g->tri_stage_run = true;
       g->raster_serial = 0;
     }
   } else if (x && V > 0) {  // no camera / filter parameters given: plain permuted download (3 planes, x first)
@@ -2439,6 +2462,7 @@ int flame_hip_mesh(flame_hip_graph* g, const float Kinv[9], const flame_hip_tri_
   fill_tri_params(Kinv, tp, &d);
   HIPCHK(launch_triangles(g->stream, V, T, g->pos, g->A[g->cur], g->tris, g->trow, g->tinc, d,
                           g->tri_normals, g->tri_valid, g->vtx_normals));
+  g->tri_stage_run = true;
   g->raster_serial = 0;  // (as in flame_hip_triangles)
   HIPCHK(launch_mesh(g->stream, V, g->pos, g->A[g->cur], g->vtx_normals, g->v_i2o_dev, d, tp->width,
                      tp->height, g->mesh_pts));
@@ -2507,6 +2531,77 @@ int flame_hip_depthmaps(flame_hip_graph* g, const float Kinv[9], const flame_hip
   if (idepthmap) HIPCHK(memcpy_sync(g->stream, idepthmap, g->map_idm, sizeof(float) * (size_t)npix, hipMemcpyDeviceToHost));
   if (depthmap) HIPCHK(memcpy_sync(g->stream, depthmap, g->map_dm, sizeof(float) * (size_t)npix, hipMemcpyDeviceToHost));
   if (cloud) HIPCHK(memcpy_sync(g->stream, cloud, g->map_cloud, sizeof(float) * 3 * (size_t)npix, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The prediction stage (upstream's project_graph): the mesh the handle still holds from the previous frame --
+// vertex pixels, idepths in the caller's units, triangles, tri_valid of the last triangle stage -- is warped into the current
+// view and z-buffered (predict.hip); reads that state and changes none of it.
+int flame_hip_predict(flame_hip_graph* g, int32_t W, int32_t H, const float K[9], const double T_world_prev[12],
+                      const double T_world_cur[12], int32_t n, const float* pix, float* prediction, int32_t* n_finite) {
+  RoctxRange roctx_("flame_hip_predict");
+  if (n_finite) *n_finite = 0;
+  if (!g || !K || !T_world_prev || !T_world_cur || W < 1 || H < 1 || W > 8192 || H > 8192 || n < 0 || (n > 0 && !pix))
+    return FLAME_HIP_ERR_ARG;
+  int rc = require_device(g);
+  if (rc) return rc;
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(K[k])) return FLAME_HIP_ERR_NAN;
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(T_world_prev[k]) || !std::isfinite(T_world_cur[k])) return FLAME_HIP_ERR_NAN;
+  if (!(K[0] > 0.f) || !(K[4] > 0.f)) return FLAME_HIP_ERR_ARG;
+  if (g->is_batch || g->plan.T <= 0 || !g->tri_stage_run) return FLAME_HIP_ERR_STATE;  // (no tri_valid to filter the mesh by)
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((rc = flame_hip_sync(g))) return rc;  // (a solve still in flight, a resident launch that gave up: the state is final behind this)
+  const int64_t npix = (int64_t)W * H;
+  if ((rc = dev_alloc(g->caps, &g->pg_key, (size_t)npix)) || (rc = dev_alloc(g->caps, &g->pg_proj, (size_t)g->V)) ||
+      (rc = dev_alloc(g->caps, &g->pg_pix, (size_t)n)) || (rc = dev_alloc(g->caps, &g->pg_pred, (size_t)n)))
+    return rc;
+  if (!g->pg_ev0) HIPCHK(hipEventCreate(&g->pg_ev0));
+  if (!g->pg_ev1) HIPCHK(hipEventCreate(&g->pg_ev1));
+  g->pg_pixels = 0;
+  PgFrame f;
+  f.V = g->V; f.T = g->plan.T; f.W = W; f.H = H; f.n = n;
+  f.fx = K[0]; f.fy = K[4]; f.cx = K[2]; f.cy = K[5];
+  pose_record((double)K[0], (double)K[4], (double)K[2], (double)K[5], T_world_cur, T_world_prev, &f.pose);
+  f.pos = g->pos; f.A = g->A[g->cur]; f.tris = g->tris; f.tri_valid = g->tri_valid;
+  f.proj = g->pg_proj; f.key = g->pg_key; f.pix = g->pg_pix; f.pred = g->pg_pred;
+  hipStream_t s = g->stream;
+  HIPCHK(g->pout.reserve(sizeof(float) * 3 * (size_t)n + 128));
+  float* h_pix = reinterpret_cast<float*>(g->pout.base);
+  float* h_pred = h_pix + 2 * (size_t)n + 16;
+  if (n > 0) std::memcpy(h_pix, pix, sizeof(float) * 2 * (size_t)n);
+  HIPCHK(hipEventRecord(g->pg_ev0, s));
+  if (n > 0) HIPCHK(hipMemcpyAsync(g->pg_pix, h_pix, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(g->pg_key, 0, sizeof(unsigned long long) * (size_t)npix, s));
+  pg_launch_project(s, f);
+  pg_launch_zbuffer(s, f);
+  pg_launch_sample(s, f);
+  HIPCHK(hipGetLastError());
+  if (n > 0) HIPCHK(hipMemcpyAsync(h_pred, g->pg_pred, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(g->pg_ev1, s));
+  HIPCHK(hipStreamSynchronize(s));
+  g->pg_pixels = npix;
+  int32_t nf = 0;
+  for (int32_t k = 0; k < n; ++k) nf += std::isfinite(h_pred[k]) ? 1 : 0;
+  if (prediction && n > 0) std::memcpy(prediction, h_pred, sizeof(float) * (size_t)n);
+  if (n_finite) *n_finite = nf;
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, g->pg_ev0, g->pg_ev1) == hipSuccess) g->predict_device_us = 1000.0 * ms;
+  g->predict_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+int flame_hip_predict_map(flame_hip_graph* g, float* idepthmap) {
+  if (!g || !idepthmap) return FLAME_HIP_ERR_ARG;
+  if (g->device < 0) return FLAME_HIP_ERR_NODEVICE;
+  if (g->pg_pixels <= 0 || !g->pg_key) return FLAME_HIP_ERR_STATE;  // no flame_hip_predict yet
+  HIPCHK(hipSetDevice(g->device));
+  int rc;
+  if ((rc = dev_alloc(g->caps, &g->pg_map, (size_t)g->pg_pixels))) return rc;
+  pg_launch_map(g->stream, g->pg_pixels, g->pg_key, g->pg_map);
+  HIPCHK(hipGetLastError());
+  HIPCHK(memcpy_sync(g->stream, idepthmap, g->pg_map, sizeof(float) * (size_t)g->pg_pixels, hipMemcpyDeviceToHost));
   return 0;
 }
 

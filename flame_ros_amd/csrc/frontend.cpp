@@ -90,25 +90,6 @@ bool finite12(const double* T) {
   return true;
 }
 
-// A = K R, c = K t of T_cur_ref = T_world_cur^-1 T_world_ref, in double, each entry rounded once to float32.
-// (Sums run left to right; tests/frontend_ref.py pose_record() is the same statement.)
-void pose_record(const flame_hip_frontend* fe, const double* Tc, const double* Tr, FePose* out) {
-  double R[9], t[3];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) R[3 * i + j] = (Tc[0 * 4 + i] * Tr[0 * 4 + j] + Tc[1 * 4 + i] * Tr[1 * 4 + j]) + Tc[2 * 4 + i] * Tr[2 * 4 + j];
-    const double d0 = Tr[3] - Tc[3], d1 = Tr[7] - Tc[7], d2 = Tr[11] - Tc[11];
-    t[i] = (Tc[0 * 4 + i] * d0 + Tc[1 * 4 + i] * d1) + Tc[2 * 4 + i] * d2;
-  }
-  for (int j = 0; j < 3; ++j) {
-    out->A[0 + j] = (float)(fe->fx * R[0 + j] + fe->cx * R[6 + j]);
-    out->A[3 + j] = (float)(fe->fy * R[3 + j] + fe->cy * R[6 + j]);
-    out->A[6 + j] = (float)R[6 + j];
-  }
-  out->c[0] = (float)(fe->fx * t[0] + fe->cx * t[2]);
-  out->c[1] = (float)(fe->fy * t[1] + fe->cy * t[2]);
-  out->c[2] = (float)t[2];
-}
-
 unsigned long long valid_mask(const flame_hip_frontend* fe) {
   unsigned long long m = 0;
   for (int p = 0; p < fe->max_poseframes; ++p)
@@ -252,7 +233,7 @@ int flame_hip_frontend_track(flame_hip_frontend* fe, const flame_hip_frontend_pa
   f.cur_pf = cur;
   f.cur = fe->d_imgs + (size_t)cur * npix;
   for (int p = 0; p < fe->max_poseframes; ++p) {
-    if (fe->pf_used[p]) pose_record(fe, T_world_cam, &fe->pf_T[12 * (size_t)p], &fe->h_poses[p]);
+    if (fe->pf_used[p]) pose_record(fe->fx, fe->fy, fe->cx, fe->cy, T_world_cam, &fe->pf_T[12 * (size_t)p], &fe->h_poses[p]);
     else std::memset(&fe->h_poses[p], 0, sizeof(FePose));
   }
   for (int32_t y = 0; y < H; ++y) std::memcpy(fe->h_img + (size_t)y * W, img + (size_t)y * pitch, (size_t)W);

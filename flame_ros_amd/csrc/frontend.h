@@ -22,6 +22,26 @@ struct FePose {
   float c[3];
 };
 
+// A = K R, c = K t of T_cur_ref = T_world_cur^-1 T_world_ref (row-major [R|t]), in double, each entry rounded once to float32.
+// (Sums run left to right; tests/frontend_ref.py pose_record() is the same statement.)  The front end's pose table and the
+// prediction stage (predict.h) both take their warp from here.
+inline void pose_record(double fx, double fy, double cx, double cy, const double* Tc, const double* Tr, FePose* out) {
+  double R[9], t[3];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[3 * i + j] = (Tc[0 * 4 + i] * Tr[0 * 4 + j] + Tc[1 * 4 + i] * Tr[1 * 4 + j]) + Tc[2 * 4 + i] * Tr[2 * 4 + j];
+    const double d0 = Tr[3] - Tc[3], d1 = Tr[7] - Tc[7], d2 = Tr[11] - Tc[11];
+    t[i] = (Tc[0 * 4 + i] * d0 + Tc[1 * 4 + i] * d1) + Tc[2 * 4 + i] * d2;
+  }
+  for (int j = 0; j < 3; ++j) {
+    out->A[0 + j] = (float)(fx * R[0 + j] + cx * R[6 + j]);
+    out->A[3 + j] = (float)(fy * R[3 + j] + cy * R[6 + j]);
+    out->A[6 + j] = (float)R[6 + j];
+  }
+  out->c[0] = (float)(fx * t[0] + cx * t[2]);
+  out->c[1] = (float)(fy * t[1] + cy * t[2]);
+  out->c[2] = (float)t[2];
+}
+
 // one emitted feature (the frame's output record, compacted in ascending slot order)
 struct FeOut {
   float x, y, mu, var;

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "raster_rules.h"
 
 namespace flamehip {
 namespace {
@@ -1307,12 +1308,7 @@ __device__ __forceinline__ float edge_w(float ax, float ay, float bx, float by, 
   return a_first ? edge_fn(ax, ay, bx, by, px, py) : -edge_fn(bx, by, ax, ay, px, py);
 }
 
-// The bounding box along one axis of n pixels: clamped to [-1, n] in float before the conversion to int
-// (a vertex beyond 2^31 px must not reach the conversion; oracle raster_span), then to the image.
-__device__ __forceinline__ void raster_span(float lo, float hi, int n, int& i0, int& i1) {
-  i0 = max((int)ceilf(fminf(fmaxf(lo, -1.0f), (float)n)), 0);
-  i1 = min((int)floorf(fminf(fmaxf(hi, -1.0f), (float)n)), n - 1);
-}
+// (raster_span, the bounding box along one axis: raster_rules.h -- shared with the prediction stage, predict.hip)
 
 // LPT lanes per triangle: 64 for meshes of large triangles (1.2 k vertices on 640 x 480: ~130 pixels
 // each), 8 for dense ones (a 50 k-vertex mesh has 3-pixel triangles: a wave per triangle kept 9 lanes

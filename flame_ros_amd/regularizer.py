@@ -345,6 +345,32 @@ class GraphRegularizer:
                  "flame_hip_depthmaps")
         return idm, dm, cl
 
+    def predict(self, W, H, K, T_world_prev, T_world_cur, pix):
+        """The prediction stage (flame_hip_predict): the mesh this handle holds -- the previous frame, behind its triangle
+        stage -- warped into the view at T_world_cur (3x4 [R|t], float64) and z-buffered; returns the inverse-depth
+        prediction at every query pixel pix[n, 2] (float32[n], NaN = none), i.e. what sync_features(prediction=...) takes.
+        `last_predicted` holds the number of finite ones."""
+        K = _f32(K).reshape(9)
+        Tp = np.ascontiguousarray(T_world_prev, np.float64).reshape(12)
+        Tc = np.ascontiguousarray(T_world_cur, np.float64).reshape(12)
+        pix = _f32(pix).reshape(-1, 2)
+        out = np.empty(len(pix), np.float32)
+        nf = C.c_int32()
+        _l.check(self._lib.flame_hip_predict(self._h, int(W), int(H), _ptr(K), _ptr(Tp), _ptr(Tc), len(pix),
+                                             _ptr(pix) if len(pix) else None, _ptr(out) if len(pix) else None, C.byref(nf)),
+                 "flame_hip_predict")
+        self.last_predicted = nf.value
+        return out
+
+    def predicted_map(self, W, H):
+        """The dense predicted idepth map of the last predict(W, H, ...) call: float32[H, W], NaN where empty."""
+        out = np.empty((int(H), int(W)), np.float32)
+        npix = self.info("predict_pixels")
+        if npix != out.size:
+            raise ValueError("the last predict() made a map of %d pixels, not %d x %d" % (npix, W, H))
+        _l.check(self._lib.flame_hip_predict_map(self._h, _ptr(out)), "flame_hip_predict_map")
+        return out
+
     def graph_filter(self, kind, passes=1):
         """Row a9: median (kind 0) / low-pass (kind 1) filter of the vertex idepths."""
         _l.check(self._lib.flame_hip_graph_filter(self._h, int(kind), int(passes)), "flame_hip_graph_filter")

@@ -133,6 +133,7 @@ class Flame {
     std::lock_guard<std::mutex> lock(mtx_);
     stats_.tock("update_locking");
     stats_.tick("update");
+    have_last_pose_ = false;  // (the mesh this call commits has no pose: nothing for project_graph to warp from)
     const bool ok = updateGraphLocked(time, img_id, vtx, idepth_mu, idepth_var, triangles, prediction, nullptr);
     stats_.tock("update");
     return ok;
@@ -179,6 +180,14 @@ class Flame {
   bool getDepthMapAndCloud(std::vector<float>* depthmap, std::vector<float>* cloud_xyz,
                            float min_depth, float max_depth) const {
     return maps(1, nullptr, depthmap, cloud_xyz, min_depth, max_depth);
+  }
+  // The dense idepth map the last update's prediction stage made (Params::project_graph): the previous frame's mesh seen from
+  // that update's pose, NaN where it shows nothing.  false when no update has run the stage yet.
+  bool getPredictedInverseDepthMap(std::vector<float>* idepthmap) const {
+    std::lock_guard<std::mutex> lock(mtx_);
+    if (!idepthmap || !predicted_map_valid_) return false;
+    idepthmap->assign(static_cast<size_t>(width_) * height_, 0.f);
+    return flame_hip_predict_map(graph_.handle(), idepthmap->data()) == 0;
   }
   // Mesh as flame_ros publishes it (row f1; reference src/utils.cc:184-230): 12 floats per
   // vertex in flame_ros::PointNormalUV layout and reversed-winding faces of the valid triangles.
@@ -272,6 +281,28 @@ class Flame {
             }
         }
         const FeatureSet& g = (ok && nk != n) ? gated : fs;
+        // ---- project_graph (Params::project_graph): the previous frame's mesh, still on the device, warped into this view;
+        // it has to read that state before the graph sync replaces it (the triangulation below has scratch of its own) ----
+        double T_cur[12];
+        poseToRt(in.pose, T_cur);
+        const bool predict = ok && params_.project_graph && params_.init_with_prediction && g.prediction.empty() &&
+                             device_frame_valid_ && have_last_pose_;
+        if (predict) {
+          stats_.tick("project_graph");
+          static_assert(sizeof(Point2f) == 2 * sizeof(float), "boundary types are packed");
+          const int32_t nq = static_cast<int32_t>(g.vtx.size());
+          predicted_.resize(g.vtx.size());
+          int32_t n_finite = 0;
+          const int rc = flame_hip_predict(graph_.handle(), width_, height_, K_, last_pose_, T_cur, nq,
+                                           nq ? reinterpret_cast<const float*>(g.vtx.data()) : nullptr, predicted_.data(), &n_finite);
+          stats_.tock("project_graph");
+          int64_t dev_us = 0;  // (device time of the stage's launches, as nltgv2_device is the solve's)
+          if (!rc && flame_hip_get_info(graph_.handle(), "predict_device_us", &dev_us) == 0)
+            stats_.setTiming("project_graph_device", 1e-3 * static_cast<double>(dev_us));
+          stats_.set("predicted", rc ? 0 : n_finite);
+          predicted_map_valid_ = rc == 0;
+          if (rc) { stats_.set("hip_error", rc); ok = false; }
+        }
         std::vector<Triangle> tris;
         tris.swap(tri_buf_);  // (last frame's list: its storage -- and, on the GPU branch, its elements -- are reused:
                               // resizing a fresh vector to 2 V triangles would clear 2 V triangles first, every frame)
@@ -304,7 +335,11 @@ class Flame {
         }
         if (ok)
           ok = updateGraphLocked(in.time, in.img_id, g.vtx, g.idepth_mu, g.idepth_var, tris,
-                                 g.prediction.empty() ? nullptr : &g.prediction, &fs);
+                                 predict ? &predicted_ : g.prediction.empty() ? nullptr : &g.prediction, &fs);
+        if (ok) {  // the pose the committed frame's mesh belongs to
+          std::memcpy(last_pose_, T_cur, sizeof(last_pose_));
+          have_last_pose_ = true;
+        }
         tris_in_library_ = false;  // (also when the graph update was not reached)
         tri_buf_.swap(tris);
       }
@@ -534,6 +569,10 @@ class Flame {
   utils::DelaunayTriangulator delaunay_;  // the built-in triangulation on the host (Params::triangulate_on_gpu = false; scratch kept across frames)
   optimizers::nltgv2_l1_graph_regularizer::Graph graph_;
   bool device_frame_valid_ = false;  // the device state belongs to the committed frame
+  double last_pose_[12] = {0.0};     // T_world_cam of the last successful update(): the view the device's mesh belongs to
+  bool have_last_pose_ = false;      // (an updateGraph() in between has no pose: the stage waits for the next update())
+  std::vector<float> predicted_;     // project_graph: the prediction per gated feature of the frame in flight
+  bool predicted_map_valid_ = false; // the library holds a predicted map (getPredictedInverseDepthMap)
   std::vector<Point2f> vtx_, raw_vtx_;
   std::vector<float> raw_mu_, raw_var_, idepths_, normals_flat_;
   std::vector<Triangle> tris_;

@@ -91,21 +91,8 @@ class GpuFrontEnd {
     last_error_ = flame_hip_frontend_prune(handle_, static_cast<int32_t>(keep_ids.size()), keep_ids.data());
   }
 
-  // [R|t], row-major 3x4 in double, from the pose's unit quaternion (normalised again in double) and translation
-  static void toRt(const SE3f& pose, double T[12]) {
-#ifdef FLAME_HAVE_SOPHUS
-    double x = pose.unit_quaternion().x(), y = pose.unit_quaternion().y(), z = pose.unit_quaternion().z(), w = pose.unit_quaternion().w();
-    const double t[3] = {pose.translation()(0), pose.translation()(1), pose.translation()(2)};
-#else
-    double x = pose.q[0], y = pose.q[1], z = pose.q[2], w = pose.q[3];
-    const double t[3] = {pose.t[0], pose.t[1], pose.t[2]};
-#endif
-    const double n = std::sqrt(((x * x + y * y) + z * z) + w * w);
-    x /= n; y /= n; z /= n; w /= n;
-    T[0] = 1.0 - 2.0 * (y * y + z * z); T[1] = 2.0 * (x * y - z * w);       T[2] = 2.0 * (x * z + y * w);        T[3] = t[0];
-    T[4] = 2.0 * (x * y + z * w);       T[5] = 1.0 - 2.0 * (x * x + z * z); T[6] = 2.0 * (y * z - x * w);        T[7] = t[1];
-    T[8] = 2.0 * (x * z - y * w);       T[9] = 2.0 * (y * z + x * w);       T[10] = 1.0 - 2.0 * (x * x + y * y); T[11] = t[2];
-  }
+  // [R|t], row-major 3x4 in double (flame/types.h poseToRt, shared with Flame's prediction stage)
+  static void toRt(const SE3f& pose, double T[12]) { poseToRt(pose, T); }
 
  private:
   bool fail(int code) {

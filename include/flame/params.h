@@ -58,6 +58,12 @@ struct Params {
   // feature's star from exact predicates; same contract as the host triangulator, which stays the choice when false).
   // A registered FrontEnd::triangulate takes precedence over both.
   bool triangulate_on_gpu = true;
+  // (this build's own) the stage upstream times as `project_graph`: before the graph sync the previous frame's regularised,
+  // validity-filtered mesh, still on the device, is warped into the new camera view and z-buffered (flame_hip_predict), and what
+  // it shows at every gated feature becomes the `prediction` the regulariser starts from.  Acts under init_with_prediction,
+  // when the front end gave no prediction of its own and the previous update succeeded; update() only (updateGraph() has no
+  // pose).  Off by default: with it off every frame starts from the features' own idepths, as before.
+  bool project_graph = false;
   // features (:209-231)
   bool do_letterbox = false;
   float min_grad_mag = 5.0f;

@@ -298,6 +298,29 @@ int flame_hip_depthmaps(flame_hip_graph* g, const float Kinv[9], const flame_hip
                         int32_t filtered, float min_depth, float max_depth, float* idepthmap,
                         float* depthmap, float* cloud);
 
+/* The prediction stage (upstream's `project_graph`, a timing key of reference src/utils.cc:143-156; the algorithm is this
+ * build's own statement, DESIGN.md 5.4, restated operation by operation in tests/predict_ref.py, which the GPU equals bit for
+ * bit): the mesh the handle STILL HOLDS from the previous frame -- vertex pixels, idepths in the caller's units (i.e. behind
+ * flame_hip_frame_results / flame_hip_scale_state under rescale_data), triangles, tri_valid of the last triangle stage run on
+ * the handle -- is warped by T_cur_prev = T_world_cur^-1 T_world_prev (row-major 3x4 [R|t] in double) into the current view of
+ * the W x H camera K (row-major 3x3 pinhole) and z-buffered: valid triangles whose three vertices project in front of the
+ * camera and that keep their orientation, nearest surface per pixel, ties to the smaller triangle id.  prediction[i] (n, may
+ * be NULL) = the inverse depth of that surface's triangle evaluated at the exact query pixel pix[2i], pix[2i+1] (looked up at
+ * the nearest integer pixel), NaN outside the image, on an empty pixel or when not finite and > 0; *n_finite (may be NULL) =
+ * how many are finite.  This is the `prediction` flame_hip_graph_sync accepts.  n = 0 is legal: only the map is made.
+ * float32 without fused multiply-add.  Reads the handle's state and changes none of it; runs on the handle's stream; synchronises.
+ * Errors: ARG (NULL, W / H outside 1 .. 8192, n < 0, fx or fy <= 0), NAN (non-finite pose or K), STATE (no graph uploaded, a
+ * batch of graphs, a graph without triangles, or no triangle stage -- flame_hip_triangles, _frame_results, _mesh, _depthmaps,
+ * _debug_image -- since the last upload: tri_valid does not exist then), NODEVICE.
+ * flame_hip_predict_map: the dense map of the last flame_hip_predict (W x H floats of THAT call, row-major): the idepth of the
+ * nearest surface at every pixel centre, NaN where empty; it stays readable across later uploads.  STATE before the first one.
+ * flame_hip_get_info: "predict_us" (host time of the last flame_hip_predict), "predict_device_us" (HIP events around its device work),
+ * "predict_pixels" (W x H of the map flame_hip_predict_map hands out, 0 = none yet). */
+int flame_hip_predict(flame_hip_graph* g, int32_t W, int32_t H, const float K[9], const double T_world_prev[12],
+                      const double T_world_cur[12], int32_t n, const float* pix /* 2n */, float* prediction /* n, may be NULL */,
+                      int32_t* n_finite /* may be NULL */);
+int flame_hip_predict_map(flame_hip_graph* g, float* idepthmap /* W*H */);
+
 /* Results out (any pointer may be NULL).  Caller's vertex/edge order.  Synchronises. */
 int flame_hip_download(flame_hip_graph* g, float* x, float* w1, float* w2, float* q);
 int flame_hip_download_bar(flame_hip_graph* g, float* xb, float* w1b, float* w2b);

@@ -11,6 +11,8 @@
 //   `repeats` times to ONE flame::Flame (every frame is a new graph for the library: nothing of a
 //   previous frame's topology is reused).  getters: 0 = update only, 1 = + getInverseDepthMesh,
 //   2 = + the three default debug images.  Prints one JSON line.
+//   FLAME_BENCH_PROJECT_GRAPH=1 (implies FLAME_BENCH_FRONTEND=1): Params::project_graph on, the camera drifts sideways by
+//   2 mm per frame, so every frame but the first warps the previous frame's mesh (project_graph_ms / _device_us in the JSON).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -73,6 +75,7 @@ int main(int argc, char** argv) {
   }
   if (const char* e = std::getenv("FLAME_BENCH_TRI_GPU")) params.triangulate_on_gpu = e[0] == '1';  // A/B: built-in triangulation on the GPU / on the host pool
   if (const char* e = std::getenv("FLAME_BENCH_TRI_THREADS")) params.triangulate_threads = std::atoi(e);
+  if (const char* e = std::getenv("FLAME_BENCH_PROJECT_GRAPH")) params.project_graph = e[0] == '1';  // A/B: the prediction stage
   flame::Matrix3f K, Kinv;  // cfg/kinect.yaml: 525/525/319.5/239.5
   K(0, 0) = 525.f; K(0, 1) = 0.f; K(0, 2) = 319.5f; K(1, 0) = 0.f; K(1, 1) = 525.f; K(1, 2) = 239.5f;
   K(2, 0) = 0.f; K(2, 1) = 0.f; K(2, 2) = 1.f;
@@ -85,7 +88,9 @@ int main(int argc, char** argv) {
   // frame's features and NO triangulate(): the built-in triangulator (on the GPU, flame_hip_delaunay, or flame/utils/delaunay.h on the host) runs
   // inside update(), as it does for a caller that only brings features
   const char* fe_env = std::getenv("FLAME_BENCH_FRONTEND");
-  const bool with_frontend = fe_env && fe_env[0] == '1';
+  const char* pg_env = std::getenv("FLAME_BENCH_PROJECT_GRAPH");
+  const bool project_graph = pg_env && pg_env[0] == '1';
+  const bool with_frontend = project_graph || (fe_env && fe_env[0] == '1');
   const Frame* cur = nullptr;
   if (with_frontend) {
     flame::FrontEnd fe;
@@ -99,7 +104,7 @@ int main(int argc, char** argv) {
   flame::SE3f pose;
   pose.q[0] = pose.q[1] = pose.q[2] = 0.f; pose.q[3] = 1.f;
   pose.t[0] = pose.t[1] = pose.t[2] = 0.f;
-  std::vector<double> upd, sync, solve, wall, get, tri;
+  std::vector<double> upd, sync, solve, wall, get, tri, pg, pg_dev, predicted;
   std::vector<flame::Point2f> ovtx;
   std::vector<float> oid;
   std::vector<flame::Vector3f> normals;
@@ -116,6 +121,7 @@ int main(int argc, char** argv) {
       const Frame& f = frames[k];
       const auto t0 = std::chrono::steady_clock::now();
       cur = &f;
+      if (project_graph) pose.t[0] = 0.002f * static_cast<float>(n);
       const bool ok = with_frontend ? sensor->update(0.033 * n, static_cast<uint32_t>(n), pose, gray, false)
                                     : sensor->updateGraph(0.033 * n, static_cast<uint32_t>(n), f.vtx, f.mu, f.var, f.tris);
       const auto t1 = std::chrono::steady_clock::now();
@@ -154,6 +160,9 @@ int main(int argc, char** argv) {
       sync.push_back(sensor->stats().timings("sync_graph"));
       solve.push_back(sensor->stats().timings("nltgv2"));
       tri.push_back(with_frontend ? sensor->stats().timings("triangulate") : 0.0);
+      pg.push_back(project_graph ? sensor->stats().timings("project_graph") : 0.0);
+      pg_dev.push_back(project_graph ? 1e3 * sensor->stats().timings("project_graph_device") : 0.0);
+      predicted.push_back(project_graph ? sensor->stats().stats("predicted") : 0.0);
       wall.push_back(std::chrono::duration<double, std::milli>(t1 - t0).count());
       get.push_back(std::chrono::duration<double, std::milli>(t2 - t1).count());
     }
@@ -167,10 +176,12 @@ int main(int argc, char** argv) {
       "\"update_ms\": {\"p50\": %.4f, \"p10\": %.4f, \"p90\": %.4f, \"max\": %.4f}, "
       "\"update_wall_ms_p50\": %.4f, \"sync_graph_ms_p50\": %.4f, \"nltgv2_ms_p50\": %.4f, "
       "\"nltgv2_device_ms\": %.4f, \"getters_ms_p50\": %.4f, \"coverage\": %.6f, \"checksum\": %lu, \"x_hash\": \"%016llx\", "
-      "\"triangulate_ms_p50\": %.4f, \"resident_frames\": %d, \"recovered_frames\": %d}\n",
+      "\"triangulate_ms_p50\": %.4f, \"resident_frames\": %d, \"recovered_frames\": %d, "
+      "\"project_graph\": %d, \"project_graph_ms_p50\": %.4f, \"project_graph_device_us_p50\": %.1f, \"predicted_p50\": %.0f}\n",
       static_cast<int>(frames[0].vtx.size()), static_cast<int>(frames[0].tris.size()),
       static_cast<int>(sensor->stats().stats("num_edges")), iters, static_cast<int>(upd.size()), getters,
       pct(upd, 0.5), pct(upd, 0.1), pct(upd, 0.9), pct(upd, 1.0), pct(wall, 0.5), pct(sync, 0.5), pct(solve, 0.5),
-      sensor->stats().timings("nltgv2_device"), pct(get, 0.5), sensor->stats().stats("coverage"), checksum, x_hash, pct(tri, 0.5), resident_frames, recovered_frames);
+      sensor->stats().timings("nltgv2_device"), pct(get, 0.5), sensor->stats().stats("coverage"), checksum, x_hash, pct(tri, 0.5), resident_frames, recovered_frames,
+      project_graph ? 1 : 0, pct(pg, 0.5), pct(pg_dev, 0.5), pct(predicted, 0.5));
   return 0;
 }

@@ -18,6 +18,7 @@
 //     (K, the distortion coefficients and the depth scale come from the sensor.yaml files, as in the reference)
 // -> one line per frame:
 //   frame <id> time <t> ok <0|1> feats <n> vtx <n> tris <n> edges <n> coverage <c> cost_smooth <s> cost_data <d> rms_vs_truth <r> update_ms <ms> ...
+// --project-graph: Params::project_graph on (every frame's solve starts from the previous mesh warped into its view).
 // --dump dir: frame_<id>.bin = {int32 V, T; float pos[2V], idepth_mu[V], idepth_var[V]; int32 tris[3T]; float idepth[V]}:
 // what went into the regulariser and what came out, for a bit-for-bit comparison with the oracle (tests).
 #include <cmath>
@@ -132,12 +133,13 @@ int main(int argc, char** argv) {
   Lite L;
   for (int k = 1; k < argc; ++k) {
     if (!std::strcmp(argv[k], "--dump") && k + 1 < argc) L.dump_dir = argv[++k];
+    else if (!std::strcmp(argv[k], "--project-graph")) L.params.project_graph = true;  // warm-start every frame from the last mesh
     else args.push_back(argv[k]);
   }
   const bool asl = !args.empty() && !std::strcmp(args[0], "asl");
   if (!args.empty() && (!std::strcmp(args[0], "tum") || asl)) args.erase(args.begin());
   if ((asl && args.size() < 4) || (!asl && args.size() < 6)) {
-    std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir]\n",
+    std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph]\n",
                  argv[0], argv[0]);
     return 2;
   }
