@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "delaunay_dev.h"
+#include "evaluate.h"
 #include "kernels.h"
 #include "plan.h"
 #include "plan_dev.h"
@@ -344,6 +345,21 @@ struct flame_hip_graph {
   float* pg_map = nullptr;
   hipEvent_t pg_ev0 = nullptr, pg_ev1 = nullptr;
   double predict_us = 0.0, predict_device_us = 0.0;
+  // evaluate stage (flame_hip_photo_reference / _photo_error / _truth_stats, evaluate.h): two dense images -- ev_img[ev_cmp]
+  // the comparison frame, the other one the current image of the last photo_error call (promoted without a second upload) --,
+  // the uploaded map / depth, the error map, the words and the partials; kept across frames, re-allocated only when W x H grows
+  uint8_t* ev_img[2] = {nullptr, nullptr};
+  int ev_cmp = 0;
+  bool ev_has_ref = false, ev_has_cur = false;
+  int32_t ev_ref_W = 0, ev_ref_H = 0, ev_cur_W = 0, ev_cur_H = 0;
+  double ev_ref_pose[12] = {0.0}, ev_cur_pose[12] = {0.0};
+  float* ev_map = nullptr;
+  float* ev_depth = nullptr;
+  float* ev_err = nullptr;
+  unsigned long long* ev_words = nullptr;
+  double* ev_partial = nullptr;
+  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+  double photo_us = 0.0, photo_device_us = 0.0, truth_us = 0.0;
   // graph filter scratch (row a9)
   float* filter_tmp = nullptr;
   // mesh output (row f1)
@@ -503,13 +519,14 @@ struct flame_hip_graph {
     pin_in.release();
     pout.release();
     map_pixels = 0;
+    ev_has_ref = ev_has_cur = false;
     n_send_v = n_send_e = n_recv_v = n_recv_e = 0;
   }
 };
 
 extern "C" {
 
-int flame_hip_version(void) { return 404; }  // (404: the prediction stage, flame_hip_predict / _predict_map; 403: the feature front end, flame_hip_frontend_*; 402, r06: halo view, peer transport, local communicator, handle options instead of environment switches)
+int flame_hip_version(void) { return 405; }  // (405: the evaluate stage, flame_hip_photo_reference / _photo_error / _truth_stats; 404: the prediction stage, flame_hip_predict / _predict_map; 403: the feature front end, flame_hip_frontend_*; 402, r06: halo view, peer transport, local communicator, handle options instead of environment switches)
 
 const char* flame_hip_strerror(int code) {
   switch (code) {
@@ -582,6 +599,8 @@ void flame_hip_graph_destroy(flame_hip_graph* g) {
     if (g->ev_state) (void)hipEventDestroy(g->ev_state);
     if (g->pg_ev0) (void)hipEventDestroy(g->pg_ev0);
     if (g->pg_ev1) (void)hipEventDestroy(g->pg_ev1);
+    if (g->ev_t0) (void)hipEventDestroy(g->ev_t0);
+    if (g->ev_t1) (void)hipEventDestroy(g->ev_t1);
     if (g->stream_in) { (void)hipStreamSynchronize(g->stream_in); (void)hipStreamDestroy(g->stream_in); }
     if (g->stream) (void)hipStreamDestroy(g->stream);
   }
@@ -818,6 +837,10 @@ int flame_hip_get_info(const flame_hip_graph* g, const char* key, int64_t* value
   else if (k == "predict_us") *value = (int64_t)(g->predict_us + 0.5);  // flame_hip_predict: host time of the last call / HIP events around its device work
   else if (k == "predict_device_us") *value = (int64_t)(g->predict_device_us + 0.5);
   else if (k == "predict_pixels") *value = g->pg_pixels;  // W x H of the map flame_hip_predict_map hands out (0 = none yet)
+  else if (k == "photo_us") *value = (int64_t)(g->photo_us + 0.5);  // flame_hip_photo_error: host time of the last call / HIP events around its device work
+  else if (k == "photo_device_us") *value = (int64_t)(g->photo_device_us + 0.5);
+  else if (k == "photo_reference") *value = g->ev_has_ref ? 1 : 0;  // a comparison frame is held
+  else if (k == "truth_us") *value = (int64_t)(g->truth_us + 0.5);  // flame_hip_truth_stats: host time of the last call
   else if (k == "lds_bytes") *value = g->opt.lds_bytes;
   else if (k == "num_cus") *value = g->num_cus;
   else if (k == "clock_khz") {  // peak engine clock of the handle's device (timeline cycles -> time)
@@ -2602,6 +2625,189 @@ int flame_hip_predict_map(flame_hip_graph* g, float* idepthmap) {
   pg_launch_map(g->stream, g->pg_pixels, g->pg_key, g->pg_map);
   HIPCHK(hipGetLastError());
   HIPCHK(memcpy_sync(g->stream, idepthmap, g->pg_map, sizeof(float) * (size_t)g->pg_pixels, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- The evaluate stage (evaluate.h): reads the solver state and changes none of it ----
+
+static bool ev_finite12(const double* T) {
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(T[k])) return false;
+  return true;
+}
+
+// what both calls do before any device work: the device, a solve in flight, and (map == nullptr) the handle's own raster
+static int ev_enter(flame_hip_graph* g, const float Kinv[9], const flame_hip_tri_params* tp, int32_t filtered, bool own_map) {
+  if (g->device < 0) return FLAME_HIP_ERR_NODEVICE;
+  if (own_map && (!g->uploaded || g->is_batch || g->plan.T <= 0)) return FLAME_HIP_ERR_STATE;  // (nothing to rasterise)
+  HIPCHK(hipSetDevice(g->device));
+  int rc;
+  if (g->uploaded && (rc = flame_hip_sync(g))) return rc;  // (the state is final, the page-locked arena free, behind this)
+  if (!g->ev_t0) HIPCHK(hipEventCreate(&g->ev_t0));
+  if (!g->ev_t1) HIPCHK(hipEventCreate(&g->ev_t1));
+  if (own_map && (rc = ensure_raster(g, Kinv, tp, filtered ? 1 : 0, 0.f, 0.f, false, false))) return rc;
+  return 0;
+}
+
+// H rows of W bytes, `pitch` apart, packed into dst
+static void ev_pack_rows(uint8_t* dst, const uint8_t* img, int32_t W, int32_t H, int32_t pitch) {
+  if (pitch == W) { std::memcpy(dst, img, (size_t)W * H); return; }
+  for (int32_t i = 0; i < H; ++i) std::memcpy(dst + (size_t)i * W, img + (size_t)i * pitch, (size_t)W);
+}
+
+int flame_hip_photo_reference(flame_hip_graph* g, int32_t W, int32_t H, const uint8_t* img, int32_t pitch,
+                              const double T_world_cam[12]) {
+  RoctxRange roctx_("flame_hip_photo_reference");
+  if (!g || W < 1 || H < 1 || W > 8192 || H > 8192) return FLAME_HIP_ERR_ARG;
+  if (img && (!T_world_cam || pitch < W)) return FLAME_HIP_ERR_ARG;
+  if (img && !ev_finite12(T_world_cam)) return FLAME_HIP_ERR_NAN;
+  if (g->device < 0) return FLAME_HIP_ERR_NODEVICE;
+  if (!img) {  // promote the current image and pose of the last flame_hip_photo_error call: the two buffers change roles
+    if (!g->ev_has_cur || g->ev_cur_W != W || g->ev_cur_H != H) return FLAME_HIP_ERR_STATE;
+    g->ev_cmp ^= 1;
+    g->ev_ref_W = W; g->ev_ref_H = H;
+    std::memcpy(g->ev_ref_pose, g->ev_cur_pose, sizeof(g->ev_ref_pose));
+    g->ev_has_ref = true;
+    g->ev_has_cur = false;
+    return 0;
+  }
+  HIPCHK(hipSetDevice(g->device));
+  int rc;
+  if (g->uploaded && (rc = flame_hip_sync(g))) return rc;
+  const size_t npix = (size_t)W * H;
+  g->ev_has_ref = false;
+  if ((rc = dev_alloc(g->caps, &g->ev_img[g->ev_cmp], npix))) return rc;
+  HIPCHK(g->pout.reserve(npix + 64));
+  ev_pack_rows(reinterpret_cast<uint8_t*>(g->pout.base), img, W, H, pitch);
+  HIPCHK(memcpy_sync(g->stream, g->ev_img[g->ev_cmp], g->pout.base, npix, hipMemcpyHostToDevice));
+  g->ev_ref_W = W; g->ev_ref_H = H;
+  std::memcpy(g->ev_ref_pose, T_world_cam, sizeof(g->ev_ref_pose));
+  g->ev_has_ref = true;
+  return 0;
+}
+
+int flame_hip_photo_error(flame_hip_graph* g, const float K[9], const float Kinv[9], const flame_hip_tri_params* tp,
+                          int32_t filtered, const float* idepthmap, const uint8_t* img, int32_t pitch,
+                          const double T_world_cam[12], uint64_t* total256, int64_t counts[4], float* error_map) {
+  RoctxRange roctx_("flame_hip_photo_error");
+  if (total256) *total256 = 0;
+  if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  if (!g || !K || !tp || !img || !T_world_cam || !total256 || !counts || (!idepthmap && !Kinv)) return FLAME_HIP_ERR_ARG;
+  const int32_t W = tp->width, H = tp->height;
+  if (W < 1 || H < 1 || W > 8192 || H > 8192 || pitch < W) return FLAME_HIP_ERR_ARG;
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(K[k]) || (!idepthmap && !std::isfinite(Kinv[k]))) return FLAME_HIP_ERR_NAN;
+  if (!ev_finite12(T_world_cam)) return FLAME_HIP_ERR_NAN;
+  if (!(K[0] > 0.f) || !(K[4] > 0.f)) return FLAME_HIP_ERR_ARG;
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc;
+  if ((rc = ev_enter(g, Kinv, tp, filtered, idepthmap == nullptr))) return rc;
+  if (!g->ev_has_ref || g->ev_ref_W != W || g->ev_ref_H != H) return FLAME_HIP_ERR_STATE;  // no comparison frame (of this size)
+  const size_t npix = (size_t)W * H;
+  const int cur = g->ev_cmp ^ 1;
+  g->ev_has_cur = false;
+  if ((rc = dev_alloc(g->caps, &g->ev_img[cur], npix)) || (rc = dev_alloc(g->caps, &g->ev_words, (size_t)kEvPhotoWords)) ||
+      (idepthmap && (rc = dev_alloc(g->caps, &g->ev_map, npix))) || (error_map && (rc = dev_alloc(g->caps, &g->ev_err, npix))))
+    return rc;
+  // page-locked arena: words | map (when uploaded) | error map (when asked for) | image
+  auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  const size_t off_map = al(sizeof(unsigned long long) * kEvPhotoWords);
+  const size_t off_err = off_map + al(idepthmap ? sizeof(float) * npix : 0);
+  const size_t off_img = off_err + al(error_map ? sizeof(float) * npix : 0);
+  HIPCHK(g->pout.reserve(off_img + npix + 64));
+  char* host = g->pout.base;
+  if (idepthmap) std::memcpy(host + off_map, idepthmap, sizeof(float) * npix);
+  ev_pack_rows(reinterpret_cast<uint8_t*>(host + off_img), img, W, H, pitch);
+  EvPhoto f;
+  f.W = W; f.H = H;
+  f.fx = K[0]; f.fy = K[4]; f.cx = K[2]; f.cy = K[5];
+  pose_record((double)K[0], (double)K[4], (double)K[2], (double)K[5], g->ev_ref_pose, T_world_cam, &f.pose);  // T_cmp_cur
+  f.idepth = idepthmap ? g->ev_map : g->map_idm;
+  f.cur = g->ev_img[cur]; f.cmp = g->ev_img[g->ev_cmp];
+  f.words = g->ev_words;
+  f.err = error_map ? g->ev_err : nullptr;
+  hipStream_t s = g->stream;
+  HIPCHK(hipEventRecord(g->ev_t0, s));
+  HIPCHK(hipMemcpyAsync(g->ev_img[cur], host + off_img, npix, hipMemcpyHostToDevice, s));
+  if (idepthmap) HIPCHK(hipMemcpyAsync(g->ev_map, host + off_map, sizeof(float) * npix, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(g->ev_words, 0, sizeof(unsigned long long) * kEvPhotoWords, s));
+  ev_launch_photo(s, f);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(host, g->ev_words, sizeof(unsigned long long) * kEvPhotoWords, hipMemcpyDeviceToHost, s));
+  if (error_map) HIPCHK(hipMemcpyAsync(host + off_err, g->ev_err, sizeof(float) * npix, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(g->ev_t1, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const unsigned long long* w = reinterpret_cast<const unsigned long long*>(host);
+  *total256 = (uint64_t)w[kEvTotal256];
+  counts[0] = (int64_t)w[kEvEvaluated]; counts[1] = (int64_t)w[kEvNoIdepth];
+  counts[2] = (int64_t)w[kEvBehind]; counts[3] = (int64_t)w[kEvOutside];
+  if (error_map) std::memcpy(error_map, host + off_err, sizeof(float) * npix);
+  g->ev_cur_W = W; g->ev_cur_H = H;
+  std::memcpy(g->ev_cur_pose, T_world_cam, sizeof(g->ev_cur_pose));
+  g->ev_has_cur = true;
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, g->ev_t0, g->ev_t1) == hipSuccess) g->photo_device_us = 1000.0 * ms;
+  g->photo_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+int flame_hip_truth_stats(flame_hip_graph* g, const float Kinv[9], const flame_hip_tri_params* tp, int32_t filtered,
+                          const float* idepthmap, const float* depth_true, int64_t confusion[4], double* total_error,
+                          float* idepth_error_map) {
+  RoctxRange roctx_("flame_hip_truth_stats");
+  if (total_error) *total_error = 0.0;
+  if (confusion) confusion[0] = confusion[1] = confusion[2] = confusion[3] = 0;
+  if (!g || !tp || !depth_true || !confusion || !total_error || (!idepthmap && !Kinv)) return FLAME_HIP_ERR_ARG;
+  const int32_t W = tp->width, H = tp->height;
+  if (W < 1 || H < 1 || W > 8192 || H > 8192) return FLAME_HIP_ERR_ARG;
+  if (!idepthmap)
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(Kinv[k])) return FLAME_HIP_ERR_NAN;
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc;
+  if ((rc = ev_enter(g, Kinv, tp, filtered, idepthmap == nullptr))) return rc;
+  const size_t npix = (size_t)W * H;
+  const int nb = ev_num_blocks((int64_t)npix);
+  if ((rc = dev_alloc(g->caps, &g->ev_depth, npix)) || (rc = dev_alloc(g->caps, &g->ev_words, (size_t)kEvPhotoWords)) ||
+      (rc = dev_alloc(g->caps, &g->ev_partial, (size_t)nb)) || (idepthmap && (rc = dev_alloc(g->caps, &g->ev_map, npix))) ||
+      (idepth_error_map && (rc = dev_alloc(g->caps, &g->ev_err, npix))))
+    return rc;
+  // page-locked arena: words | partials | error map (when asked for) | depth | map (when uploaded)
+  auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  const size_t off_part = al(sizeof(unsigned long long) * kEvTruthWords);
+  const size_t off_err = off_part + al(sizeof(double) * (size_t)nb);
+  const size_t off_depth = off_err + al(idepth_error_map ? sizeof(float) * npix : 0);
+  const size_t off_map = off_depth + al(sizeof(float) * npix);
+  HIPCHK(g->pout.reserve(off_map + (idepthmap ? sizeof(float) * npix : 0) + 64));
+  char* host = g->pout.base;
+  std::memcpy(host + off_depth, depth_true, sizeof(float) * npix);
+  if (idepthmap) std::memcpy(host + off_map, idepthmap, sizeof(float) * npix);
+  EvTruth f;
+  f.npix = (int64_t)npix;
+  f.idepth = idepthmap ? g->ev_map : g->map_idm;
+  f.depth = g->ev_depth;
+  f.words = g->ev_words;
+  f.partial = g->ev_partial;
+  f.err = idepth_error_map ? g->ev_err : nullptr;
+  hipStream_t s = g->stream;
+  HIPCHK(hipMemcpyAsync(g->ev_depth, host + off_depth, sizeof(float) * npix, hipMemcpyHostToDevice, s));
+  if (idepthmap) HIPCHK(hipMemcpyAsync(g->ev_map, host + off_map, sizeof(float) * npix, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(g->ev_words, 0, sizeof(unsigned long long) * kEvTruthWords, s));
+  ev_launch_truth(s, f);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(host, g->ev_words, sizeof(unsigned long long) * kEvTruthWords, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(host + off_part, g->ev_partial, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s));
+  if (idepth_error_map) HIPCHK(hipMemcpyAsync(host + off_err, g->ev_err, sizeof(float) * npix, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const unsigned long long* w = reinterpret_cast<const unsigned long long*>(host);
+  confusion[0] = (int64_t)w[kEvTruePos]; confusion[1] = (int64_t)w[kEvTrueNeg];
+  confusion[2] = (int64_t)w[kEvFalsePos]; confusion[3] = (int64_t)w[kEvFalseNeg];
+  const double* part = reinterpret_cast<const double*>(host + off_part);
+  double total = 0.0;
+  for (int b = 0; b < nb; ++b) total = total + part[b];  // ascending b: the last leg of the fixed summation shape (evaluate.h)
+  *total_error = total;
+  if (idepth_error_map) std::memcpy(idepth_error_map, host + off_err, sizeof(float) * npix);
+  g->truth_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
   return 0;
 }
 

@@ -79,6 +79,10 @@ SYMBOLS = {
     "flame_hip_depthmaps": (C.c_int, [_VP, _VP, C.POINTER(TriParams), _I32, C.c_float, C.c_float, _VP, _VP, _VP]),
     "flame_hip_predict": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _VP, C.POINTER(_I32)]),
     "flame_hip_predict_map": (C.c_int, [_VP, _VP]),
+    "flame_hip_photo_reference": (C.c_int, [_VP, _I32, _I32, _VP, _I32, _VP]),
+    "flame_hip_photo_error": (C.c_int, [_VP, _VP, _VP, C.POINTER(TriParams), _I32, _VP, _VP, _I32, _VP, C.POINTER(C.c_uint64),
+                                        _VP, _VP]),
+    "flame_hip_truth_stats": (C.c_int, [_VP, _VP, C.POINTER(TriParams), _I32, _VP, _VP, _VP, C.POINTER(C.c_double), _VP]),
     "flame_hip_download": (C.c_int, [_VP] + [_VP] * 4),
     "flame_hip_download_bar": (C.c_int, [_VP] + [_VP] * 3),
     "flame_hip_halo_register": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _VP, _I32, _VP]),

@@ -49,6 +49,16 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _rows_u8(img):
+    """(uint8 array [H, W] whose rows are contiguous, its pitch in bytes): a padded view goes through without a copy."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise ValueError("a grey image is uint8[H, W]")
+    if img.shape[1] > 1 and img.strides[1] != 1 or img.shape[0] > 1 and img.strides[0] < img.shape[1]:
+        img = np.ascontiguousarray(img)
+    return img, int(img.strides[0]) if img.shape[0] > 1 else int(img.shape[1])
+
+
 class GraphRegularizer:
     """One Delaunay vertex graph resident on one GPU (a `flame_hip_graph` handle)."""
 
@@ -370,6 +380,58 @@ class GraphRegularizer:
             raise ValueError("the last predict() made a map of %d pixels, not %d x %d" % (npix, W, H))
         _l.check(self._lib.flame_hip_predict_map(self._h, _ptr(out)), "flame_hip_predict_map")
         return out
+
+    def photo_reference(self, img, T_world):
+        """The evaluate stage's comparison frame (flame_hip_photo_reference): img uint8[H, W] (rows may be padded: a view
+        with contiguous rows is passed with its pitch) and its pose T_world (3x4 [R|t], float64).  img=None promotes the
+        image and pose of the last photo_error() call; it then takes that call's size."""
+        if img is None:
+            W, H = getattr(self, "_photo_size", (1, 1))
+            _l.check(self._lib.flame_hip_photo_reference(self._h, W, H, None, 0, None), "flame_hip_photo_reference")
+            return
+        img, pitch = _rows_u8(img)
+        T = np.ascontiguousarray(T_world, np.float64).reshape(12)
+        H, W = img.shape
+        _l.check(self._lib.flame_hip_photo_reference(self._h, W, H, img.ctypes.data_as(C.c_void_p), pitch, _ptr(T)),
+                 "flame_hip_photo_reference")
+
+    def photo_error(self, img, T_world, K, Kinv, tri_params, idepthmap=None, filtered=True, want_map=False):
+        """Photometric error of a dense idepth map against the comparison frame (flame_hip_photo_error): img uint8[H, W]
+        at pose T_world; idepthmap float32[H, W] (NaN = none) or None = this handle's own dense map (filtered or not).
+        Returns (total256, counts[, error_map]): the error in grey levels x 256 as an int, the pixel counts (evaluated,
+        no_idepth, behind, outside) as ints, and with want_map the per-pixel error float32[H, W] (NaN = not evaluated)."""
+        img, pitch = _rows_u8(img)
+        H, W = tri_params.height, tri_params.width
+        if img.shape != (H, W):
+            raise ValueError("image is %s, tri_params say %d x %d" % (img.shape, H, W))
+        K = _f32(K).reshape(9)
+        Kinv = None if Kinv is None else _f32(Kinv).reshape(9)
+        T = np.ascontiguousarray(T_world, np.float64).reshape(12)
+        idm = None if idepthmap is None else _f32(idepthmap).reshape(H, W)
+        err = np.empty((H, W), np.float32) if want_map else None
+        total, counts = C.c_uint64(), np.zeros(4, np.int64)
+        _l.check(self._lib.flame_hip_photo_error(self._h, _ptr(K), _ptr(Kinv), C.byref(tri_params), int(filtered), _ptr(idm),
+                                                 img.ctypes.data_as(C.c_void_p), pitch, _ptr(T), C.byref(total), _ptr(counts),
+                                                 _ptr(err)), "flame_hip_photo_error")
+        self._photo_size = (W, H)
+        out = (int(total.value), tuple(int(c) for c in counts))
+        return out + (err,) if want_map else out
+
+    def truth_stats(self, depth_true, Kinv, tri_params, idepthmap=None, filtered=True, want_map=False):
+        """Ground-truth statistics of a dense idepth map (flame_hip_truth_stats; reference getDepthConfusionMatrix):
+        depth_true float32[H, W] (> 0 = there is truth).  Returns (confusion, total_error[, error_map]): (true_pos,
+        true_neg, false_pos, false_neg) as ints, the summed idepth error as a float, and with want_map the per-pixel
+        error float32[H, W]."""
+        H, W = tri_params.height, tri_params.width
+        depth = _f32(depth_true).reshape(H, W)
+        Kinv = None if Kinv is None else _f32(Kinv).reshape(9)
+        idm = None if idepthmap is None else _f32(idepthmap).reshape(H, W)
+        err = np.empty((H, W), np.float32) if want_map else None
+        total, conf = C.c_double(), np.zeros(4, np.int64)
+        _l.check(self._lib.flame_hip_truth_stats(self._h, _ptr(Kinv), C.byref(tri_params), int(filtered), _ptr(idm),
+                                                 _ptr(depth), _ptr(conf), C.byref(total), _ptr(err)), "flame_hip_truth_stats")
+        out = (tuple(int(c) for c in conf), float(total.value))
+        return out + (err,) if want_map else out
 
     def graph_filter(self, kind, passes=1):
         """Row a9: median (kind 0) / low-pass (kind 1) filter of the vertex idepths."""

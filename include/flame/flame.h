@@ -79,6 +79,17 @@ struct FrontEnd {
   // pose-frame bookkeeping (optional)
   std::function<void(const std::vector<uint32_t>&, const std::vector<SE3f>&)> updatePoseFramePoses;
   std::function<void(const std::vector<uint32_t>&)> prunePoseFrames;
+  // the front end's own stat keys of the frame (optional; called after a successful `track`, under the mutex update() holds)
+  std::function<void(utils::StatsTracker*)> reportStats;
+};
+
+// Ground-truth statistics of the committed frame's filtered dense idepth map (Flame::getTruthStats): the confusion matrix and
+// summed idepth error of getDepthConfusionMatrix (reference src/utils.cc:326-368), and what the reference front end derives
+// from them (src/flame_offline_tum.cc:331-334, float division as there: 0 / 0 reads as NaN).
+struct TruthStats {
+  int64_t true_pos = 0, true_neg = 0, false_pos = 0, false_neg = 0;
+  double total_error = 0.0;  // summed in double in a fixed shape on the device (flame_hip.h, flame_hip_truth_stats)
+  float avg_error = 0.f, precision = 0.f, recall = 0.f;
 };
 
 class Flame {
@@ -189,6 +200,29 @@ class Flame {
     idepthmap->assign(static_cast<size_t>(width_) * height_, 0.f);
     return flame_hip_predict_map(graph_.handle(), idepthmap->data()) == 0;
   }
+  // The truth columns of the reference's stats.txt (src/flame_offline_tum.cc:365-372,383-390) for the committed frame:
+  // depth_true holds width x height depths, row-major, > 0 where there is truth; idepth_error (optional) gets the per-pixel
+  // |idepth - 1 / depth| resp. |idepth|, NaN where the reference leaves NaN.  Computed on the GPU (flame_hip_truth_stats) from
+  // the filtered dense map, the one getFilteredInverseDepthMap hands out.  false when there is no committed frame, the size
+  // does not fit or the library fails.
+  bool getTruthStats(const std::vector<float>& depth_true, TruthStats* out, std::vector<float>* idepth_error = nullptr) const {
+    std::lock_guard<std::mutex> lock(mtx_);
+    if (!out || !device_frame_valid_ || depth_true.size() != static_cast<size_t>(width_) * height_) return false;
+    const flame_hip_tri_params tp = triParams();
+    if (idepth_error) idepth_error->assign(depth_true.size(), 0.f);
+    int64_t conf[4] = {0, 0, 0, 0};
+    double total = 0.0;
+    if (flame_hip_truth_stats(graph_.handle(), Kinv_, &tp, 1, nullptr, depth_true.data(), conf, &total,
+                              idepth_error ? idepth_error->data() : nullptr))
+      return false;
+    out->true_pos = conf[0]; out->true_neg = conf[1]; out->false_pos = conf[2]; out->false_neg = conf[3];
+    out->total_error = total;
+    const float detections = static_cast<float>(conf[0] + conf[2]);
+    out->avg_error = static_cast<float>(total) / detections;
+    out->precision = static_cast<float>(conf[0]) / detections;
+    out->recall = static_cast<float>(conf[0]) / static_cast<float>(conf[0] + conf[3]);
+    return true;
+  }
   // Mesh as flame_ros publishes it (row f1; reference src/utils.cc:184-230): 12 floats per
   // vertex in flame_ros::PointNormalUV layout and reversed-winding faces of the valid triangles.
   bool getMeshPointNormalUV(std::vector<float>* points, std::vector<int32_t>* faces) const {
@@ -261,6 +295,7 @@ class Flame {
            fs.idepth_var.size() == fs.vtx.size() &&
            (fs.prediction.empty() || fs.prediction.size() == fs.vtx.size());
       stats_.tock("update_idepths");
+      if (ok && frontend_.reportStats) frontend_.reportStats(&stats_);  // num_idepth_updates, num_fail_* (src/utils.cc:124-129)
       if (ok) {
         // variance gate (row a7): "Maximum idepth var before feature can be added to graph"
         // (reference cfg/flame_offline_tum.yaml:92)
@@ -268,6 +303,7 @@ class Flame {
         std::vector<uint8_t> keep(fs.vtx.size());
         const int32_t nk = flame_hip_feature_gate(n, fs.idepth_var.data(), params_.idepth_var_max_graph, keep.data());
         ok = nk >= 0;
+        if (ok) stats_.set("num_fail_max_var", n - nk);  // (src/utils.cc:125)
         FeatureSet gated;
         if (ok && nk != n) {  // (every feature through the gate -- the usual frame -- is used where it lies)
           gated.vtx.reserve(nk); gated.idepth_mu.reserve(nk); gated.idepth_var.reserve(nk);
@@ -340,6 +376,7 @@ class Flame {
           std::memcpy(last_pose_, T_cur, sizeof(last_pose_));
           have_last_pose_ = true;
         }
+        if (ok && params_.photo_error && in.img) ok = photoErrorLocked(in, T_cur);
         tris_in_library_ = false;  // (also when the graph update was not reached)
         tri_buf_.swap(tris);
       }
@@ -478,6 +515,47 @@ class Flame {
     return true;
   }
 
+  // The evaluate stage of update() (Params::photo_error), behind a committed frame: the photometric error of its filtered dense
+  // map against the comparison frame -- the most recent pose frame BEFORE this frame ([UPSTREAM-RECALL] for the idea: upstream
+  // scores a frame against the pose frame its features come from) --, then, on a pose frame, this frame becomes the comparison
+  // frame (its image is on the device already when the error was computed).  A failing call fails the update (stats key
+  // "hip_error"); the frame's mesh stays committed.
+  bool photoErrorLocked(const FrameInput& in, const double T_cur[12]) {
+    if (in.img->rows != height_ || in.img->cols != width_) return failPhoto(FLAME_HIP_ERR_ARG);
+    const uint8_t* row0 = in.img->ptr<uint8_t>(0);
+    const int32_t pitch = height_ > 1 ? static_cast<int32_t>(in.img->ptr<uint8_t>(1) - row0) : width_;
+    uint64_t total256 = 0;
+    int64_t counts[4] = {0, 0, 0, 0};
+    if (photo_reference_valid_) {
+      stats_.tick("photo_error");
+      const flame_hip_tri_params tp = triParams();
+      const int rc = flame_hip_photo_error(graph_.handle(), K_, Kinv_, &tp, 1, nullptr, row0, pitch, T_cur, &total256, counts, nullptr);
+      stats_.tock("photo_error");
+      if (rc) return failPhoto(rc);
+      int64_t dev_us = 0;
+      if (flame_hip_get_info(graph_.handle(), "photo_device_us", &dev_us) == 0)
+        stats_.setTiming("photo_error_device", 1e-3 * static_cast<double>(dev_us));
+    }
+    const double total = static_cast<double>(total256) / 256.0;
+    stats_.set("total_photo_error", total);
+    stats_.set("avg_photo_error", counts[0] > 0 ? total / static_cast<double>(counts[0]) : 0.0);
+    stats_.set("photo_pixels", static_cast<double>(counts[0]));
+    if (in.is_poseframe) {
+      const int rc = photo_reference_valid_ ? flame_hip_photo_reference(graph_.handle(), width_, height_, nullptr, 0, nullptr)
+                                            : flame_hip_photo_reference(graph_.handle(), width_, height_, row0, pitch, T_cur);
+      if (rc) return failPhoto(rc);
+      photo_reference_valid_ = true;
+    }
+    return true;
+  }
+  bool failPhoto(int code) {
+    stats_.set("hip_error", code);
+    stats_.set("total_photo_error", 0.0);
+    stats_.set("avg_photo_error", 0.0);
+    stats_.set("photo_pixels", 0.0);
+    return false;
+  }
+
   flame_hip_tri_params triParams() const {
     flame_hip_tri_params tp;
     tp.do_oblique_triangle_filter = params_.do_oblique_triangle_filter;
@@ -573,6 +651,7 @@ class Flame {
   bool have_last_pose_ = false;      // (an updateGraph() in between has no pose: the stage waits for the next update())
   std::vector<float> predicted_;     // project_graph: the prediction per gated feature of the frame in flight
   bool predicted_map_valid_ = false; // the library holds a predicted map (getPredictedInverseDepthMap)
+  bool photo_reference_valid_ = false;  // photo_error: the library holds a comparison frame (the last pose frame)
   std::vector<Point2f> vtx_, raw_vtx_;
   std::vector<float> raw_mu_, raw_var_, idepths_, normals_flat_;
   std::vector<Triangle> tris_;

@@ -6,8 +6,8 @@
 //   sensor.setFrontEnd(features.frontEnd());
 //   sensor.update(time, img_id, pose, gray, is_poseframe);   // reference src/flame_offline_tum.cc:578-579
 //
-// frontEnd() binds `track`, `updatePoseFramePoses` and `prunePoseFrames` to this object (which must outlive the Flame it feeds);
-// `triangulate` stays empty, so the library's GPU Delaunay triangulation runs.  `track` hands every emitted feature of the frame
+// frontEnd() binds `track`, `updatePoseFramePoses`, `prunePoseFrames` and `reportStats` (the tracking stat keys num_idepth_updates
+// / num_fail_*) to this object (which must outlive the Flame it feeds); `triangulate` stays empty, so the library's GPU Delaunay triangulation runs.  `track` hands every emitted feature of the frame
 // to Flame (whose variance gate selects the ones that enter the graph) and fails the frame when fewer than three are emitted.
 // Poses are T_world_cam; they cross into the library as row-major [R|t] in double, made from the unit quaternion and the
 // translation of SE3f (Sophus::SE3f when present, the fallback struct otherwise).  Nothing throws; a failure leaves its code
@@ -55,6 +55,7 @@ class GpuFrontEnd {
     fe.track = [this](const FrameInput& in, FeatureSet* out) { return track(in, out); };
     fe.updatePoseFramePoses = [this](const std::vector<uint32_t>& ids, const std::vector<SE3f>& poses) { updatePoseFramePoses(ids, poses); };
     fe.prunePoseFrames = [this](const std::vector<uint32_t>& ids) { prunePoseFrames(ids); };
+    fe.reportStats = [this](utils::StatsTracker* stats) { reportStats(stats); };
     return fe;
   }
 
@@ -89,6 +90,20 @@ class GpuFrontEnd {
   void prunePoseFrames(const std::vector<uint32_t>& keep_ids) {
     if (!handle_) return;
     last_error_ = flame_hip_frontend_prune(handle_, static_cast<int32_t>(keep_ids.size()), keep_ids.data());
+  }
+
+  // The tracking stats FlameStats carries (reference src/utils.cc:124-129), from the counts of the frame just tracked
+  // (flame_hip_frontend_info): features whose idepth was updated, features that died of too many dropouts, ambiguous matches,
+  // matches above the cost threshold.  `num_fail_max_var` is Flame's own (its variance gate); `num_fail_ref_patch_grad` has no
+  // counterpart in this front end's statement (DESIGN.md 5.3 tests no reference-patch gradient) and stays unset.
+  void reportStats(utils::StatsTracker* stats) const {
+    if (!handle_ || !stats) return;
+    static const char* const kKeys[4][2] = {{"num_idepth_updates", "ok"}, {"num_fail_max_dropouts", "died"},
+                                            {"num_fail_ambiguous_match", "ambiguous"}, {"num_fail_max_cost", "bad_match"}};
+    for (int k = 0; k < 4; ++k) {
+      int64_t v = 0;
+      if (flame_hip_frontend_info(handle_, kKeys[k][1], &v) == 0) stats->set(kKeys[k][0], static_cast<double>(v));
+    }
   }
 
   // [R|t], row-major 3x4 in double (flame/types.h poseToRt, shared with Flame's prediction stage)

@@ -64,6 +64,12 @@ struct Params {
   // when the front end gave no prediction of its own and the previous update succeeded; update() only (updateGraph() has no
   // pose).  Off by default: with it off every frame starts from the features' own idepths, as before.
   bool project_graph = false;
+  // (this build's own) the evaluate stage behind every successful update(): the photometric error of the frame's filtered
+  // dense idepth map -- the frame's image warped onto the most recent pose frame before it (flame_hip_photo_error) -- fills
+  // the stat keys `total_photo_error` / `avg_photo_error` the reference front ends read (src/flame_offline_tum.cc:391-392,
+  // src/utils.cc:138-139) and `photo_pixels`, the number of pixels evaluated.  update() only (updateGraph() has neither image
+  // nor pose).  Off by default: with it off update() makes exactly the calls it made before and none of the keys appears.
+  bool photo_error = false;
   // features (:209-231)
   bool do_letterbox = false;
   float min_grad_mag = 5.0f;

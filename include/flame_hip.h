@@ -321,6 +321,51 @@ int flame_hip_predict(flame_hip_graph* g, int32_t W, int32_t H, const float K[9]
                       int32_t* n_finite /* may be NULL */);
 int flame_hip_predict_map(flame_hip_graph* g, float* idepthmap /* W*H */);
 
+/* The evaluate stage: the pipeline's self-check (restated operation by operation in tests/eval_ref.py, which
+ * the GPU equals bit for bit).  It fills the stats the reference front ends read and nothing here set before:
+ * `total_photo_error` / `avg_photo_error` (reference src/flame_offline_tum.cc:391-392, src/utils.cc:138-139) and the
+ * confusion matrix of getDepthConfusionMatrix (reference src/utils.cc:326-368).  Both calls read the solver state and change
+ * none of it, run on the handle's stream and synchronise once; their buffers belong to the handle and are kept across frames.
+ *
+ * flame_hip_photo_reference: the comparison frame -- image (H rows of W bytes, `pitch` apart) and world pose (row-major 3x4
+ * [R|t] in double) --, kept on the device until replaced.  img == NULL promotes the image and pose of the last
+ * flame_hip_photo_error call (no second upload; pitch and T_world_cam are not read; STATE when there is none of W x H).
+ *
+ * flame_hip_photo_error: every pixel (j, i) of the current image that has an idepth xi (finite, > 0) is warped by
+ * T_cmp_cur = T_world_cmp^-1 T_world_cur into the comparison image, b = ((j - cx) / fx, (i - cy) / fy, 1),
+ * w = A b + xi c with A = K R, c = K t formed in double and rounded once, p = (w0 / w2, w1 / w2) rounded to sixteenths of a
+ * pixel; the comparison image is sampled bilinearly with integer weights (sum 256), D = |S - 256 I_cur(j, i)|.  float32
+ * without fused multiply-add; the costs are integers, so the sums are exact whatever the order.  *total256 = the sum of D
+ * (the photometric error in grey levels x 256); counts = pixels {evaluated, without idepth, behind the comparison camera,
+ * outside it (a bilinear neighbour would be)}, which sum to W x H; error_map (W*H, may be NULL) = D / 256 per pixel, NaN where
+ * not evaluated.  The map: idepthmap (host, W*H, NaN = none) or, with NULL, the handle's own dense map of the current state
+ * (filtered != 0: the filtered one) -- the one rasterisation `coverage`, the map getters and the debug images share.  With a
+ * caller's map only tp->width / height are read, Kinv may be NULL, and a handle without a graph is legal.
+ *
+ * flame_hip_truth_stats: the loop of reference src/utils.cc:339-365, branch by branch: depth_true > 0 = there is truth (NaN
+ * is none), !isnan(idepth) = there is an estimate (an infinite idepth is one), error = |idepth - 1.0f / depth| resp. |idepth|.
+ * confusion = {true_pos, true_neg, false_pos, false_neg}; idepth_error_map (W*H, may be NULL) = the error, NaN where the
+ * reference leaves NaN.  *total_error: the reference sums the float32 errors in float32 in row-major order, which no parallel
+ * kernel reproduces; here they are summed in DOUBLE in a fixed shape that depends on W x H alone (blocks of 1 024 pixels, one
+ * fixed tree each, block sums added in ascending order), so the value is a function of the inputs only and within
+ * 2 (W H - 1) 2^-53 of the exact sum, relatively.
+ *
+ * Errors: ARG (NULL, pitch < W, W / H outside 1 .. 8192, fx or fy <= 0), NAN (non-finite pose, K or Kinv) -- both before any
+ * device work --, NODEVICE, STATE (photo_error before any reference or with a reference of another size; NULL map on a handle
+ * without graph or triangles, or with a batch).
+ * flame_hip_get_info: "photo_us" / "photo_device_us" (host time of the last flame_hip_photo_error / HIP events around its
+ * device work), "photo_reference" (1 = a comparison frame is held), "truth_us" (host time of the last flame_hip_truth_stats). */
+int flame_hip_photo_reference(flame_hip_graph* g, int32_t W, int32_t H, const uint8_t* img, int32_t pitch,
+                              const double T_world_cam[12]);
+int flame_hip_photo_error(flame_hip_graph* g, const float K[9], const float Kinv[9], const flame_hip_tri_params* tp,
+                          int32_t filtered, const float* idepthmap /* host W*H, NULL = the handle's dense map */,
+                          const uint8_t* img, int32_t pitch, const double T_world_cam[12],
+                          uint64_t* total256, int64_t counts[4] /* evaluated, no_idepth, behind, outside */,
+                          float* error_map /* W*H, may be NULL */);
+int flame_hip_truth_stats(flame_hip_graph* g, const float Kinv[9], const flame_hip_tri_params* tp, int32_t filtered,
+                          const float* idepthmap /* NULL = the handle's */, const float* depth_true /* host W*H */,
+                          int64_t confusion[4] /* tp, tn, fp, fn */, double* total_error, float* idepth_error_map);
+
 /* Results out (any pointer may be NULL).  Caller's vertex/edge order.  Synchronises. */
 int flame_hip_download(flame_hip_graph* g, float* x, float* w1, float* w2, float* q);
 int flame_hip_download_bar(flame_hip_graph* g, float* xb, float* w1b, float* w2b);

@@ -19,6 +19,8 @@
 // -> one line per frame:
 //   frame <id> time <t> ok <0|1> feats <n> vtx <n> tris <n> edges <n> coverage <c> cost_smooth <s> cost_data <d> rms_vs_truth <r> update_ms <ms> ...
 // --project-graph: Params::project_graph on (every frame's solve starts from the previous mesh warped into its view).
+// --photo-error: Params::photo_error on; the frame line ends with `photo_total <sum of grey-level errors> photo_avg <per evaluated
+// pixel> photo_pixels <n>` (the frame's filtered map against the last pose frame, every tenth frame here; 0 0 0 before the first).
 // --dump dir: frame_<id>.bin = {int32 V, T; float pos[2V], idepth_mu[V], idepth_var[V]; int32 tris[3T]; float idepth[V]}:
 // what went into the regulariser and what came out, for a bit-for-bit comparison with the oracle (tests).
 #include <cmath>
@@ -118,11 +120,15 @@ struct Lite {
       }
     }
     const flame::utils::StatsTracker& st = sensor->stats();
-    std::printf("frame %u time %.6f ok %d feats %d vtx %zu tris %zu edges %zu coverage %.4f cost_smooth %.6g cost_data %.6g rms_vs_truth %.6g update_ms %.3f hip_error %d persist_used %d pose_t %.9g %.9g %.9g pose_q %.9g %.9g %.9g %.9g\n",
+    std::printf("frame %u time %.6f ok %d feats %d vtx %zu tris %zu edges %zu coverage %.4f cost_smooth %.6g cost_data %.6g rms_vs_truth %.6g update_ms %.3f hip_error %d persist_used %d pose_t %.9g %.9g %.9g pose_q %.9g %.9g %.9g %.9g",
                 id, time, ok ? 1 : 0, static_cast<int>(st.stats("num_feats")), vtx.size(), tris.size(), edges.size(),
                 st.stats("coverage"), st.stats("nltgv2_total_smoothness_cost"), st.stats("nltgv2_total_data_cost"),
                 n ? std::sqrt(se / n) : 0.0, st.timings("update"), static_cast<int>(st.stats("hip_error")),
                 static_cast<int>(st.stats("persist_used")), pose.t[0], pose.t[1], pose.t[2], pose.q[0], pose.q[1], pose.q[2], pose.q[3]);
+    if (params.photo_error)  // (appended at the end: without the flag the line is what it was)
+      std::printf(" photo_total %.6f photo_avg %.6f photo_pixels %d", st.stats("total_photo_error"), st.stats("avg_photo_error"),
+                  static_cast<int>(st.stats("photo_pixels")));
+    std::printf("\n");
   }
 };
 
@@ -134,12 +140,13 @@ int main(int argc, char** argv) {
   for (int k = 1; k < argc; ++k) {
     if (!std::strcmp(argv[k], "--dump") && k + 1 < argc) L.dump_dir = argv[++k];
     else if (!std::strcmp(argv[k], "--project-graph")) L.params.project_graph = true;  // warm-start every frame from the last mesh
+    else if (!std::strcmp(argv[k], "--photo-error")) L.params.photo_error = true;      // the evaluate stage behind every frame
     else args.push_back(argv[k]);
   }
   const bool asl = !args.empty() && !std::strcmp(args[0], "asl");
   if (!args.empty() && (!std::strcmp(args[0], "tum") || asl)) args.erase(args.begin());
   if ((asl && args.size() < 4) || (!asl && args.size() < 6)) {
-    std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph]\n",
+    std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph] [--photo-error]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph] [--photo-error]\n",
                  argv[0], argv[0]);
     return 2;
   }
