@@ -1,7 +1,9 @@
 // flame_ros_amd/csrc/frontend.cpp -- C ABI of the feature front end (include/flame_hip.h, flame_hip_frontend_*): owns the
 // pose-frame ring (images on the device, poses on the host in double), the feature slots and the per-frame scratch; a call
 // of flame_hip_frontend_track uploads the image, queues kill -> track + project -> (detect) -> assign + compact on the
-// handle's stream and returns when the emitted features are on the host.  Kernels: frontend.hip.  Reads no environment variable.
+// handle's stream and returns when the emitted features are on the host.  Kernels: frontend.hip.  With a camera set
+// (flame_hip_frontend_set_camera) flame_hip_frontend_track_raw puts the ingest stage (ingest.hip: grey, box downsample, undistort)
+// between the upload of the raw image and the tracker, writing into the ring slot the tracker reads.  Reads no environment variable.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -12,6 +14,7 @@
 
 #include "../../include/flame_hip.h"
 #include "frontend.h"
+#include "ingest.h"
 
 using namespace flamehip;
 
@@ -21,6 +24,7 @@ struct flame_hip_frontend {
   double fx = 0, fy = 0, cx = 0, cy = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t evi0 = nullptr, evi1 = nullptr;  // around the raw upload and the ingest stage
   // pose-frame ring (host side)
   std::vector<uint32_t> pf_id;
   std::vector<uint8_t> pf_used;
@@ -45,6 +49,17 @@ struct flame_hip_frontend {
   int32_t counts[kFeCounts] = {0};
   double track_us = 0.0, track_device_us = 0.0;
   bool timed = false;
+  bool have_image = false;  // fr.cur holds the image the last track / track_raw call tracked
+  // ingest stage (set_camera): raw image staging (page-locked host + device), the grey + box scratch, rectify's own output
+  bool have_cam = false;
+  InCam cam;
+  size_t raw_cap = 0;  // bytes d_raw / h_raw hold
+  uint8_t* h_raw = nullptr;
+  uint8_t* d_raw = nullptr;
+  uint8_t* d_scratch = nullptr;
+  uint8_t* d_rect = nullptr;
+  double ingest_device_us = 0.0;
+  int64_t ingest_raw_bytes = 0;
 };
 
 namespace {
@@ -77,6 +92,12 @@ void release(flame_hip_frontend* fe) {
     if (fe->h_poses) (void)hipHostFree(fe->h_poses);
     if (fe->h_counts) (void)hipHostFree(fe->h_counts);
     if (fe->h_out) (void)hipHostFree(fe->h_out);
+    if (fe->h_raw) (void)hipHostFree(fe->h_raw);
+    if (fe->d_raw) (void)hipFree(fe->d_raw);
+    if (fe->d_scratch) (void)hipFree(fe->d_scratch);
+    if (fe->d_rect) (void)hipFree(fe->d_rect);
+    if (fe->evi0) (void)hipEventDestroy(fe->evi0);
+    if (fe->evi1) (void)hipEventDestroy(fe->evi1);
     if (fe->ev0) (void)hipEventDestroy(fe->ev0);
     if (fe->ev1) (void)hipEventDestroy(fe->ev1);
     if (fe->stream) (void)hipStreamDestroy(fe->stream);
@@ -108,6 +129,30 @@ int check_params(const flame_hip_frontend_params* p) {
   return 0;
 }
 
+// the raw image, rows made dense, into the page-locked staging buffer
+void stage_raw(flame_hip_frontend* fe, const uint8_t* raw, int32_t pitch) {
+  const size_t row = (size_t)fe->cam.raw_w * in_channels(fe->cam.format);
+  for (int32_t y = 0; y < fe->cam.raw_h; ++y) std::memcpy(fe->h_raw + (size_t)y * row, raw + (size_t)y * pitch, row);
+}
+
+// Queues the upload of the staged raw image and the ingest stage on the handle's stream (no synchronisation); `dst` gets the
+// W x H rectified grey image.  The grey + box kernel is skipped for GRAY8 at resize factor 1, the remap when D is all zero.
+int queue_ingest(flame_hip_frontend* fe, uint8_t* dst) {
+  const InCam& c = fe->cam;
+  hipStream_t s = fe->stream;
+  const int32_t raw_pitch = c.raw_w * in_channels(c.format);
+  const bool box = !(c.format == kInGray8 && c.f == 1);
+  const bool remap = c.k1 != 0.f || c.k2 != 0.f || c.p1 != 0.f || c.p2 != 0.f || c.k3 != 0.f;
+  FE_HIP(hipEventRecord(fe->evi0, s));
+  uint8_t* up = (box || remap) ? fe->d_raw : dst;  // (nothing to do: the upload is the stage)
+  FE_HIP(hipMemcpyAsync(up, fe->h_raw, (size_t)raw_pitch * c.raw_h, hipMemcpyHostToDevice, s));
+  if (box) in_launch_grey_box(s, c, fe->d_raw, raw_pitch, remap ? fe->d_scratch : dst);
+  if (remap) in_launch_remap(s, c, box ? fe->d_scratch : fe->d_raw, dst);
+  FE_HIP(hipGetLastError());
+  FE_HIP(hipEventRecord(fe->evi1, s));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -131,13 +176,13 @@ int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, i
   if (!out) return FLAME_HIP_ERR_ARG;
   *out = nullptr;
   if (!K || W < 8 || H < 8 || W > 8192 || H > 8192 || max_features < 1 || max_features > (1 << 22) || max_poseframes < 1 ||
-      max_poseframes > kFeMaxPoseframes || device < 0)
+      max_poseframes > kFeMaxPoseframes || device < -1)
     return FLAME_HIP_ERR_ARG;
   for (int k = 0; k < 9; ++k)
     if (!std::isfinite(K[k])) return FLAME_HIP_ERR_NAN;
   if (!(K[0] > 0.f) || !(K[4] > 0.f)) return FLAME_HIP_ERR_ARG;
   int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || device >= n || hipSetDevice(device) != hipSuccess) return FLAME_HIP_ERR_NODEVICE;
+  if (device >= 0 && (hipGetDeviceCount(&n) != hipSuccess || device >= n || hipSetDevice(device) != hipSuccess)) return FLAME_HIP_ERR_NODEVICE;
   flame_hip_frontend* fe = new (std::nothrow) flame_hip_frontend();
   if (!fe) return FLAME_HIP_ERR_ALLOC;
   fe->device = device;
@@ -146,11 +191,16 @@ int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, i
   fe->pf_id.assign(max_poseframes, 0);
   fe->pf_used.assign(max_poseframes, 0);
   fe->pf_T.assign(12 * (size_t)max_poseframes, 0.0);
+  if (device < 0) {  // a handle without a device: arguments are checked, every call that needs the device returns NODEVICE
+    std::memset(&fe->fr, 0, sizeof(fe->fr));
+    *out = fe;
+    return 0;
+  }
   const size_t npix = (size_t)W * H, F = (size_t)max_features;
   const size_t state_bytes = 12 * ((F * 4 + 255) & ~(size_t)255) + ((F + 255) & ~(size_t)255) + ((F * sizeof(float4) + 255) & ~(size_t)255) +
                              ((F * sizeof(FeOut) + 255) & ~(size_t)255);
   bool ok = hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&fe->ev0) == hipSuccess &&
-            hipEventCreate(&fe->ev1) == hipSuccess;
+            hipEventCreate(&fe->ev1) == hipSuccess && hipEventCreate(&fe->evi0) == hipSuccess && hipEventCreate(&fe->evi1) == hipSuccess;
   ok = ok && hipMalloc(&fe->d_imgs, npix * (size_t)(max_poseframes + 1)) == hipSuccess &&
        hipMalloc(&fe->d_poses, sizeof(FePose) * (size_t)max_poseframes) == hipSuccess && hipMalloc(&fe->d_state, state_bytes) == hipSuccess &&
        hipMalloc(&fe->d_counts, sizeof(int32_t) * kFeCounts) == hipSuccess &&
@@ -185,12 +235,10 @@ void flame_hip_frontend_destroy(flame_hip_frontend* fe) {
   if (fe) release(fe);
 }
 
-int flame_hip_frontend_track(flame_hip_frontend* fe, const flame_hip_frontend_params* params, const uint8_t* img, int32_t pitch,
-                             uint32_t img_id, const double T_world_cam[12], int32_t is_poseframe, int32_t* n_out) {
-  if (!fe || !params || !img || !T_world_cam || !n_out || pitch < fe->W) return FLAME_HIP_ERR_ARG;
-  *n_out = 0;
-  if (const int rc = check_params(params)) return rc;
-  if (!finite12(T_world_cam)) return FLAME_HIP_ERR_NAN;
+// One frame (flame_hip_frontend_track / _track_raw, arguments checked by the caller): `raw` = the image goes through the ingest
+// stage of the handle's camera on its way into the ring slot, otherwise it is uploaded there as it is.
+static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* params, const uint8_t* img, int32_t pitch, bool raw,
+                     uint32_t img_id, const double T_world_cam[12], int32_t is_poseframe, int32_t* n_out) {
   const auto t0 = std::chrono::steady_clock::now();
   FE_HIP(hipSetDevice(fe->device));
   const int32_t W = fe->W, H = fe->H;
@@ -236,11 +284,16 @@ int flame_hip_frontend_track(flame_hip_frontend* fe, const flame_hip_frontend_pa
     if (fe->pf_used[p]) pose_record(fe->fx, fe->fy, fe->cx, fe->cy, T_world_cam, &fe->pf_T[12 * (size_t)p], &fe->h_poses[p]);
     else std::memset(&fe->h_poses[p], 0, sizeof(FePose));
   }
-  for (int32_t y = 0; y < H; ++y) std::memcpy(fe->h_img + (size_t)y * W, img + (size_t)y * pitch, (size_t)W);
-
   hipStream_t s = fe->stream;
-  FE_HIP(hipEventRecord(fe->ev0, s));
-  FE_HIP(hipMemcpyAsync(fe->d_imgs + (size_t)cur * npix, fe->h_img, npix, hipMemcpyHostToDevice, s));
+  if (raw) {
+    stage_raw(fe, img, pitch);
+    FE_HIP(hipEventRecord(fe->ev0, s));
+    if (const int rc = queue_ingest(fe, fe->d_imgs + (size_t)cur * npix)) return rc;
+  } else {
+    for (int32_t y = 0; y < H; ++y) std::memcpy(fe->h_img + (size_t)y * W, img + (size_t)y * pitch, (size_t)W);
+    FE_HIP(hipEventRecord(fe->ev0, s));
+    FE_HIP(hipMemcpyAsync(fe->d_imgs + (size_t)cur * npix, fe->h_img, npix, hipMemcpyHostToDevice, s));
+  }
   FE_HIP(hipMemcpyAsync(fe->d_poses, fe->h_poses, sizeof(FePose) * (size_t)fe->max_poseframes, hipMemcpyHostToDevice, s));
   FE_HIP(hipMemsetAsync(fe->d_cell_key, 0xFF, sizeof(unsigned long long) * (size_t)ncells, s));
   FE_HIP(hipMemsetAsync(fe->d_counts, 0, sizeof(int32_t) * kFeCounts, s));
@@ -265,10 +318,105 @@ int flame_hip_frontend_track(flame_hip_frontend* fe, const flame_hip_frontend_pa
     std::memcpy(&fe->pf_T[12 * (size_t)cur], T_world_cam, 12 * sizeof(double));
     ++fe->pf_added;
   }
+  fe->have_image = true;
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, fe->ev0, fe->ev1) == hipSuccess) fe->track_device_us = 1000.0 * ms;
+  fe->ingest_device_us = 0.0;
+  fe->ingest_raw_bytes = 0;
+  if (raw) {
+    if (hipEventElapsedTime(&ms, fe->evi0, fe->evi1) == hipSuccess) fe->ingest_device_us = 1000.0 * ms;
+    fe->ingest_raw_bytes = (int64_t)fe->cam.raw_h * fe->cam.raw_w * in_channels(fe->cam.format);
+  }
   fe->track_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
   *n_out = fe->n_out;
+  return 0;
+}
+
+int flame_hip_frontend_track(flame_hip_frontend* fe, const flame_hip_frontend_params* params, const uint8_t* img, int32_t pitch,
+                             uint32_t img_id, const double T_world_cam[12], int32_t is_poseframe, int32_t* n_out) {
+  if (!fe || !params || !img || !T_world_cam || !n_out || pitch < fe->W) return FLAME_HIP_ERR_ARG;
+  *n_out = 0;
+  if (const int rc = check_params(params)) return rc;
+  if (!finite12(T_world_cam)) return FLAME_HIP_ERR_NAN;
+  if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
+  return run_track(fe, params, img, pitch, false, img_id, T_world_cam, is_poseframe, n_out);
+}
+
+int flame_hip_frontend_set_camera(flame_hip_frontend* fe, const flame_hip_camera* cam) {
+  if (!fe) return FLAME_HIP_ERR_ARG;
+  if (!cam) {  // back to rectified input (the staging stays for the next camera)
+    fe->have_cam = false;
+    return 0;
+  }
+  if (cam->format < 0 || cam->format >= kInFormats || cam->resize_factor < 1 || cam->resize_factor > kInMaxResize || cam->raw_width < 1 ||
+      cam->raw_height < 1 || cam->raw_width / cam->resize_factor != fe->W || cam->raw_height / cam->resize_factor != fe->H)
+    return FLAME_HIP_ERR_ARG;
+  for (int k = 0; k < 5; ++k)
+    if (!std::isfinite(cam->D[k])) return FLAME_HIP_ERR_NAN;
+  InCam c;
+  c.raw_w = cam->raw_width; c.raw_h = cam->raw_height; c.format = cam->format; c.f = cam->resize_factor;
+  c.W = fe->W; c.H = fe->H;
+  c.fx = (float)fe->fx; c.fy = (float)fe->fy; c.cx = (float)fe->cx; c.cy = (float)fe->cy;
+  c.k1 = cam->D[0]; c.k2 = cam->D[1]; c.p1 = cam->D[2]; c.p2 = cam->D[3]; c.k3 = cam->D[4];
+  if (fe->device >= 0) {
+    FE_HIP(hipSetDevice(fe->device));
+    FE_HIP(hipStreamSynchronize(fe->stream));
+    const size_t need = (size_t)c.raw_h * c.raw_w * in_channels(c.format), npix = (size_t)fe->W * fe->H;
+    if (need > fe->raw_cap) {
+      fe->have_cam = false;
+      if (fe->h_raw) (void)hipHostFree(fe->h_raw);
+      if (fe->d_raw) (void)hipFree(fe->d_raw);
+      fe->h_raw = nullptr; fe->d_raw = nullptr; fe->raw_cap = 0;
+      if (hipHostMalloc(&fe->h_raw, need) != hipSuccess || hipMalloc(&fe->d_raw, need) != hipSuccess) return FLAME_HIP_ERR_ALLOC;
+      fe->raw_cap = need;
+    }
+    if (!fe->d_scratch && hipMalloc(&fe->d_scratch, npix) != hipSuccess) return FLAME_HIP_ERR_ALLOC;
+    if (!fe->d_rect && hipMalloc(&fe->d_rect, npix) != hipSuccess) return FLAME_HIP_ERR_ALLOC;
+  }
+  fe->cam = c;
+  fe->have_cam = true;
+  return 0;
+}
+
+int flame_hip_frontend_track_raw(flame_hip_frontend* fe, const flame_hip_frontend_params* params, const uint8_t* raw, int32_t pitch,
+                                 uint32_t img_id, const double T_world_cam[12], int32_t is_poseframe, int32_t* n_out) {
+  if (!fe || !params || !raw || !T_world_cam || !n_out) return FLAME_HIP_ERR_ARG;
+  *n_out = 0;
+  if (!fe->have_cam) return FLAME_HIP_ERR_STATE;
+  if (pitch < fe->cam.raw_w * in_channels(fe->cam.format)) return FLAME_HIP_ERR_ARG;
+  if (const int rc = check_params(params)) return rc;
+  if (!finite12(T_world_cam)) return FLAME_HIP_ERR_NAN;
+  if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
+  return run_track(fe, params, raw, pitch, true, img_id, T_world_cam, is_poseframe, n_out);
+}
+
+int flame_hip_frontend_rectify(flame_hip_frontend* fe, const uint8_t* raw, int32_t pitch, uint8_t* out, int32_t out_pitch) {
+  if (!fe || !raw || !out || out_pitch < fe->W) return FLAME_HIP_ERR_ARG;
+  if (!fe->have_cam) return FLAME_HIP_ERR_STATE;
+  if (pitch < fe->cam.raw_w * in_channels(fe->cam.format)) return FLAME_HIP_ERR_ARG;
+  if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
+  FE_HIP(hipSetDevice(fe->device));
+  const size_t npix = (size_t)fe->W * fe->H;
+  stage_raw(fe, raw, pitch);
+  if (const int rc = queue_ingest(fe, fe->d_rect)) return rc;
+  FE_HIP(hipMemcpyAsync(fe->h_img, fe->d_rect, npix, hipMemcpyDeviceToHost, fe->stream));
+  FE_HIP(hipStreamSynchronize(fe->stream));
+  for (int32_t y = 0; y < fe->H; ++y) std::memcpy(out + (size_t)y * out_pitch, fe->h_img + (size_t)y * fe->W, (size_t)fe->W);
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, fe->evi0, fe->evi1) == hipSuccess) fe->ingest_device_us = 1000.0 * ms;
+  fe->ingest_raw_bytes = (int64_t)fe->cam.raw_h * fe->cam.raw_w * in_channels(fe->cam.format);
+  return 0;
+}
+
+int flame_hip_frontend_image(flame_hip_frontend* fe, uint8_t* out, int32_t out_pitch) {
+  if (!fe || !out || out_pitch < fe->W) return FLAME_HIP_ERR_ARG;
+  if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
+  if (!fe->have_image) return FLAME_HIP_ERR_STATE;
+  FE_HIP(hipSetDevice(fe->device));
+  const size_t npix = (size_t)fe->W * fe->H;
+  FE_HIP(hipMemcpyAsync(fe->h_img, fe->fr.cur, npix, hipMemcpyDeviceToHost, fe->stream));
+  FE_HIP(hipStreamSynchronize(fe->stream));
+  for (int32_t y = 0; y < fe->H; ++y) std::memcpy(out + (size_t)y * out_pitch, fe->h_img + (size_t)y * fe->W, (size_t)fe->W);
   return 0;
 }
 
@@ -306,6 +454,7 @@ int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* 
     if (!keep) { fe->pf_used[p] = 0; dropped = true; }
   }
   if (dropped) {
+    if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
     FE_HIP(hipSetDevice(fe->device));
     fe_launch_kill(fe->stream, fe->fr, valid_mask(fe));
     FE_HIP(hipGetLastError());
@@ -317,6 +466,7 @@ int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* 
 int flame_hip_frontend_state(flame_hip_frontend* fe, uint8_t* alive, int32_t* u, int32_t* v, int32_t* poseframe, float* mu, float* var,
                              int32_t* dropouts, int32_t* status, int32_t* kstar) {
   if (!fe) return FLAME_HIP_ERR_ARG;
+  if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
   FE_HIP(hipSetDevice(fe->device));
   FE_HIP(hipStreamSynchronize(fe->stream));
   const size_t F = (size_t)fe->max_features;
@@ -343,6 +493,9 @@ int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* va
   if (!std::strcmp(key, "track_us")) { *value = (int64_t)(fe->track_us + 0.5); return 0; }
   if (!std::strcmp(key, "track_device_us")) { *value = (int64_t)(fe->track_device_us + 0.5); return 0; }
   if (!std::strcmp(key, "max_features")) { *value = fe->max_features; return 0; }
+  if (!std::strcmp(key, "ingest_device_us")) { *value = (int64_t)(fe->ingest_device_us + 0.5); return 0; }
+  if (!std::strcmp(key, "ingest_raw_bytes")) { *value = fe->ingest_raw_bytes; return 0; }
+  if (!std::strcmp(key, "camera")) { *value = fe->have_cam ? 1 : 0; return 0; }
   if (!std::strcmp(key, "poseframes")) {
     int64_t c = 0;
     for (int p = 0; p < fe->max_poseframes; ++p) c += fe->pf_used[p] ? 1 : 0;

@@ -13,6 +13,7 @@ from .lib import FlameHipError  # noqa: F401
 
 FE_OK, FE_NO_PARALLAX, FE_OUTSIDE, FE_BAD_MATCH, FE_AMBIGUOUS, FE_NEW, FE_DIED, FE_FREE = 0, 1, 2, 3, 4, 5, 6, -1
 STATUS_KEYS = ("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died")
+PIX_CHANNELS = {_l.PIX_GRAY8: 1, _l.PIX_BGR8: 3, _l.PIX_RGB8: 3, _l.PIX_BGRA8: 4, _l.PIX_RGBA8: 4}
 
 
 class FrontEndParams(C.Structure):
@@ -21,6 +22,12 @@ class FrontEndParams(C.Structure):
                 ("epipolar_line_var", C.c_float), ("max_dropouts", C.c_int32), ("idepth_min", C.c_float),
                 ("idepth_max", C.c_float), ("idepth_init", C.c_float), ("var_init", C.c_float),
                 ("max_match_error", C.c_float)]
+
+
+class Camera(C.Structure):
+    """flame_hip_camera."""
+    _fields_ = [("raw_width", C.c_int32), ("raw_height", C.c_int32), ("format", C.c_int32), ("resize_factor", C.c_int32),
+                ("D", C.c_float * 5)]
 
 
 def default_frontend_params(**overrides):
@@ -85,6 +92,53 @@ class GpuFrontEnd:
                                                     int(img_id), _ptr(T), int(bool(is_poseframe)), C.byref(n)),
                  "flame_hip_frontend_track")
         return self.features(n.value)
+
+    def set_camera(self, raw_width=None, raw_height=None, D=(0, 0, 0, 0, 0), format=_l.PIX_GRAY8, resize_factor=1):
+        """Sets the camera of the ingest stage (raw size, pixel format, integer resize factor, D = k1 k2 p1 p2 k3; the
+        handle's K is the K of the output image).  `set_camera(None)`: back to rectified input."""
+        if raw_width is None:
+            _l.check(self._lib.flame_hip_frontend_set_camera(self._h, None), "flame_hip_frontend_set_camera")
+            self._cam = None
+            return
+        cam = Camera(int(raw_width), int(raw_height), int(format), int(resize_factor), (C.c_float * 5)(*[float(d) for d in D]))
+        _l.check(self._lib.flame_hip_frontend_set_camera(self._h, C.byref(cam)), "flame_hip_frontend_set_camera")
+        self._cam = cam
+
+    def _raw(self, raw):
+        cam = getattr(self, "_cam", None)
+        raw = np.asarray(raw)
+        if cam is None:  # (the library refuses the call with STATE before it reads the image)
+            return np.ascontiguousarray(raw, np.uint8)
+        ch = PIX_CHANNELS[cam.format]
+        shape = (cam.raw_height, cam.raw_width) + ((ch,) if ch > 1 else ())
+        if raw.dtype != np.uint8 or raw.shape != shape or raw.strides[1] != ch or (ch > 1 and raw.strides[2] != 1) or \
+                raw.strides[0] < cam.raw_width * ch:
+            raise ValueError("raw must be raw_height x raw_width%s uint8 with packed pixels" % (" x %d" % ch if ch > 1 else ""))
+        return raw
+
+    def track_raw(self, params, raw, img_id, T_world_cam, is_poseframe):
+        """`track` with the ingest stage in front: `raw` is the image as the camera delivers it (any row stride)."""
+        raw = self._raw(raw)
+        T = _pose(T_world_cam)
+        n = C.c_int32()
+        _l.check(self._lib.flame_hip_frontend_track_raw(self._h, C.byref(params), C.c_void_p(raw.ctypes.data), int(raw.strides[0]),
+                                                        int(img_id), _ptr(T), int(bool(is_poseframe)), C.byref(n)),
+                 "flame_hip_frontend_track_raw")
+        return self.features(n.value)
+
+    def rectify(self, raw):
+        """The ingest stage alone: the H x W rectified grey image of `raw`; feature state and ring stay untouched."""
+        raw = self._raw(raw)
+        out = np.zeros((self.H, self.W), np.uint8)
+        _l.check(self._lib.flame_hip_frontend_rectify(self._h, C.c_void_p(raw.ctypes.data), int(raw.strides[0]), _ptr(out), self.W),
+                 "flame_hip_frontend_rectify")
+        return out
+
+    def image(self):
+        """The image the last track / track_raw call tracked (after the ingest stage)."""
+        out = np.zeros((self.H, self.W), np.uint8)
+        _l.check(self._lib.flame_hip_frontend_image(self._h, _ptr(out), self.W), "flame_hip_frontend_image")
+        return out
 
     def features(self, n=None):
         n = self.info("emitted") if n is None else n

@@ -81,6 +81,10 @@ struct FrontEnd {
   std::function<void(const std::vector<uint32_t>&)> prunePoseFrames;
   // the front end's own stat keys of the frame (optional; called after a successful `track`, under the mutex update() holds)
   std::function<void(utils::StatsTracker*)> reportStats;
+  // the frame's image as `track` saw it, when that is not FrameInput::img (optional: a front end that takes RAW camera images
+  // and rectifies them itself, GpuFrontEnd::setCamera; called after a successful `track`, under the mutex update() holds, by
+  // the stages that read pixels -- the evaluate stage; nullptr = not available, which fails that stage)
+  std::function<const Image1b*()> rectified;
 };
 
 // Ground-truth statistics of the committed frame's filtered dense idepth map (Flame::getTruthStats): the confusion matrix and
@@ -521,9 +525,12 @@ class Flame {
   // frame (its image is on the device already when the error was computed).  A failing call fails the update (stats key
   // "hip_error"); the frame's mesh stays committed.
   bool photoErrorLocked(const FrameInput& in, const double T_cur[12]) {
-    if (in.img->rows != height_ || in.img->cols != width_) return failPhoto(FLAME_HIP_ERR_ARG);
-    const uint8_t* row0 = in.img->ptr<uint8_t>(0);
-    const int32_t pitch = height_ > 1 ? static_cast<int32_t>(in.img->ptr<uint8_t>(1) - row0) : width_;
+    // (a front end that rectifies raw images itself hands out what it tracked; in.img is then the raw image, of another size)
+    const Image1b* img = frontend_.rectified ? frontend_.rectified() : in.img;
+    if (!img) return failPhoto(FLAME_HIP_ERR_STATE);
+    if (img->rows != height_ || img->cols != width_) return failPhoto(FLAME_HIP_ERR_ARG);
+    const uint8_t* row0 = img->ptr<uint8_t>(0);
+    const int32_t pitch = height_ > 1 ? static_cast<int32_t>(img->ptr<uint8_t>(1) - row0) : width_;
     uint64_t total256 = 0;
     int64_t counts[4] = {0, 0, 0, 0};
     if (photo_reference_valid_) {

@@ -12,6 +12,12 @@
 // Poses are T_world_cam; they cross into the library as row-major [R|t] in double, made from the unit quaternion and the
 // translation of SE3f (Sophus::SE3f when present, the fallback struct otherwise).  Nothing throws; a failure leaves its code
 // in lastError() (and the frame fails, which Flame reports like any failed update).
+//
+// RAW camera images: features.setCamera(raw_width, raw_height, resize_factor, D) before sensor.setFrontEnd(features.frontEnd())
+// puts the library's ingest stage (integer downsample, plumb-bob undistortion; flame_hip.h, flame_hip_frontend_set_camera) in
+// front of the tracker: update() then takes the grey image as the camera delivers it, raw_width x raw_height, and the K both
+// objects were made with is the K of the rectified image (K_raw / resize_factor).  frontEnd() binds `rectified` as well, so the
+// stages of Flame that read pixels (the evaluate stage) get the rectified image, downloaded once per frame and only when asked.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -56,18 +62,63 @@ class GpuFrontEnd {
     fe.updatePoseFramePoses = [this](const std::vector<uint32_t>& ids, const std::vector<SE3f>& poses) { updatePoseFramePoses(ids, poses); };
     fe.prunePoseFrames = [this](const std::vector<uint32_t>& ids) { prunePoseFrames(ids); };
     fe.reportStats = [this](utils::StatsTracker* stats) { reportStats(stats); };
+    if (have_camera_) fe.rectified = [this]() { return rectified(); };
     return fe;
+  }
+
+  // The ingest stage: raw GRAY8 images of raw_width x raw_height (update() takes an Image1b), downsampled by the integer
+  // resize_factor to this object's width x height and undistorted with D = (k1, k2, p1, p2, k3) onto this object's K.  Call it
+  // before frontEnd().  false (lastError()) when the library refuses the camera.
+  bool setCamera(int raw_width, int raw_height, int resize_factor, const float D[5]) {
+    if (!handle_) return false;
+    flame_hip_camera cam;
+    cam.raw_width = raw_width; cam.raw_height = raw_height; cam.format = FLAME_HIP_PIX_GRAY8; cam.resize_factor = resize_factor;
+    for (int k = 0; k < 5; ++k) cam.D[k] = D[k];
+    last_error_ = flame_hip_frontend_set_camera(handle_, &cam);
+    have_camera_ = last_error_ == 0;
+    if (have_camera_) { raw_width_ = raw_width; raw_height_ = raw_height; }
+    return have_camera_;
+  }
+  bool hasCamera() const { return have_camera_; }
+
+  // The ingest stage alone (flame_hip_frontend_rectify): `out` becomes the width x height rectified image of `raw`; the
+  // feature state is untouched.
+  bool rectify(const Image1b& raw, Image1b* out) {
+    if (!handle_) return false;
+    if (!have_camera_) return fail(FLAME_HIP_ERR_STATE);
+    if (!out || raw.rows != raw_height_ || raw.cols != raw_width_) return fail(FLAME_HIP_ERR_ARG);
+    if (out->rows != height_ || out->cols != width_) *out = Image1b(height_, width_);
+    const int rc = flame_hip_frontend_rectify(handle_, raw.ptr<uint8_t>(0), pitchOf(raw), out->ptr<uint8_t>(0), pitchOf(*out));
+    if (rc) return fail(rc);
+    last_error_ = 0;
+    return true;
+  }
+
+  // The image the last track() tracked (after the ingest stage), downloaded on the first call after that track(); nullptr
+  // (lastError()) when there is none.
+  const Image1b* rectified() {
+    if (!handle_) return nullptr;
+    if (!rectified_valid_) {
+      if (rectified_.rows != height_ || rectified_.cols != width_) rectified_ = Image1b(height_, width_);
+      const int rc = flame_hip_frontend_image(handle_, rectified_.ptr<uint8_t>(0), pitchOf(rectified_));
+      if (rc) { last_error_ = rc; return nullptr; }
+      rectified_valid_ = true;
+    }
+    return &rectified_;
   }
 
   bool track(const FrameInput& in, FeatureSet* out) {
     if (!handle_) return false;  // (lastError() still holds why the handle could not be made)
-    if (!in.img || !out || in.img->rows != height_ || in.img->cols != width_) return fail(FLAME_HIP_ERR_ARG);
+    rectified_valid_ = false;
+    const int rows = have_camera_ ? raw_height_ : height_, cols = have_camera_ ? raw_width_ : width_;
+    if (!in.img || !out || in.img->rows != rows || in.img->cols != cols) return fail(FLAME_HIP_ERR_ARG);
     double T[12];
     toRt(in.pose, T);
     const uint8_t* row0 = in.img->ptr<uint8_t>(0);
-    const int32_t pitch = height_ > 1 ? static_cast<int32_t>(in.img->ptr<uint8_t>(1) - row0) : width_;
+    const int32_t pitch = pitchOf(*in.img);
     int32_t n = 0;
-    int rc = flame_hip_frontend_track(handle_, &fparams_, row0, pitch, in.img_id, T, in.is_poseframe ? 1 : 0, &n);
+    int rc = have_camera_ ? flame_hip_frontend_track_raw(handle_, &fparams_, row0, pitch, in.img_id, T, in.is_poseframe ? 1 : 0, &n)
+                          : flame_hip_frontend_track(handle_, &fparams_, row0, pitch, in.img_id, T, in.is_poseframe ? 1 : 0, &n);
     if (rc) return fail(rc);
     static_assert(sizeof(Point2f) == 2 * sizeof(float), "boundary types are packed");
     out->vtx.resize(static_cast<size_t>(n));
@@ -114,7 +165,14 @@ class GpuFrontEnd {
     last_error_ = code;
     return false;
   }
+  static int32_t pitchOf(const Image1b& img) {
+    return img.rows > 1 ? static_cast<int32_t>(img.ptr<uint8_t>(1) - img.ptr<uint8_t>(0)) : img.cols;
+  }
   int width_, height_;
+  bool have_camera_ = false;
+  int raw_width_ = 0, raw_height_ = 0;
+  Image1b rectified_;             // the image of the last track(), downloaded on demand
+  bool rectified_valid_ = false;
   flame_hip_frontend_params fparams_;
   flame_hip_frontend* handle_ = nullptr;
   int last_error_ = 0;

@@ -521,8 +521,10 @@ enum {
   FLAME_HIP_FE_DIED = 6         /* dropout counter exceeded max_dropouts in this frame: the slot is free again */
 };
 void flame_hip_frontend_default_params(flame_hip_frontend_params* p);
-/* K row-major 3x3 pinhole (fx = K[0], fy = K[4], cx = K[2], cy = K[5]); images arrive rectified.  8 <= W, H <= 8192;
- * max_poseframes <= 64.  Device memory: (max_poseframes + 1) W H bytes + ~100 bytes per feature slot. */
+/* K row-major 3x3 pinhole (fx = K[0], fy = K[4], cx = K[2], cy = K[5]); images arrive rectified unless a camera is set
+ * (flame_hip_frontend_set_camera below).  8 <= W, H <= 8192; max_poseframes <= 64.  Device memory: (max_poseframes + 1) W H
+ * bytes + ~100 bytes per feature slot.  device = -1 makes a handle without a device: arguments are checked as usual and every
+ * call that needs the device returns NODEVICE. */
 int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, int32_t H, const float K[9], int32_t max_features,
                               int32_t max_poseframes);
 void flame_hip_frontend_destroy(flame_hip_frontend* fe);
@@ -544,12 +546,45 @@ int flame_hip_frontend_set_poses(flame_hip_frontend* fe, int32_t n, const uint32
 int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* keep_ids);
 /* keys: "live", "poseframes", "emitted", "track_us" (host time of the last frame's call), "track_device_us" (HIP events around
  * its device work); features of the last frame per status: "ok", "no_parallax", "outside", "bad_match", "ambiguous", "new",
- * "died"; "detections_dropped" (no free slot), "max_features" */
+ * "died"; "detections_dropped" (no free slot), "max_features"; "camera" (1 = a camera is set), "ingest_device_us" (HIP events
+ * around the raw upload and the ingest stage of the last _track_raw / _rectify; 0 after a _track), "ingest_raw_bytes" (what that
+ * call uploaded) */
 int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value);
 /* Debug/test hook: every slot's state (max_features entries each; any pointer may be NULL): alive, reference pixel (u, v),
  * ring slot of its pose frame, prior (mu, var) in the pose frame, dropout counter, last status (-1 = free), last best sample. */
 int flame_hip_frontend_state(flame_hip_frontend* fe, uint8_t* alive, int32_t* u, int32_t* v, int32_t* poseframe, float* mu, float* var,
                              int32_t* dropouts, int32_t* status, int32_t* kstar);
+
+/* ---- ingest stage (opt-in): raw camera images in front of the tracker.  With a camera set, _track_raw takes the image as the
+ * camera delivers it and runs three steps on the handle's stream between the upload and the tracker, each rounded to uint8
+ * (restated in tests/ingest_ref.py, which the GPU equals bit for bit):
+ *   1. grey: GRAY8 as is; BGR8 / RGB8 / BGRA8 / RGBA8 by (4899 R + 9617 G + 1868 B + 8192) >> 14, alpha ignored;
+ *   2. downsample by the integer resize_factor f (1..8): W = raw_width / f, H = raw_height / f (integer division, trailing raw
+ *      rows and columns ignored) must be the handle's size; pixel (x, y) = (sum of the f x f block at (f x, f y) + f f / 2) / (f f);
+ *   3. undistort with the handle's K -- the K of the OUTPUT image: a caller that resizes passes K / f -- and D = (k1, k2, p1, p2,
+ *      k3): distortPoint() / undistort<uint8_t>() of include/flame_ros/image_io.h operation for operation, float32 without
+ *      fused multiply-add, bilinear, (uint8)(val + 0.5f).  All five coefficients exactly 0: the step is skipped.  The output is 0
+ *      unless the source position (su, sv) has su > -1 && su < W && sv > -1 && sv < H, tested in float (a NaN or infinite
+ *      position gives 0); inside that range taps outside the image read 0.
+ * Without a camera every call does what it did before.  There is no CPU path. */
+enum { FLAME_HIP_PIX_GRAY8 = 0, FLAME_HIP_PIX_BGR8, FLAME_HIP_PIX_RGB8, FLAME_HIP_PIX_BGRA8, FLAME_HIP_PIX_RGBA8 };
+typedef struct {
+  int32_t raw_width, raw_height, format, resize_factor;
+  float D[5]; /* k1, k2, p1, p2, k3 (OpenCV order) */
+} flame_hip_camera;
+/* Sets the handle's camera and allocates the page-locked staging and the device buffers of the raw image; NULL: back to
+ * rectified input.  Errors: ARG (size mismatch, resize_factor outside 1..8, unknown format), NAN (non-finite D), ALLOC.  On a
+ * handle without a device the camera is recorded (so that the other calls check their arguments against it). */
+int flame_hip_frontend_set_camera(flame_hip_frontend* fe, const flame_hip_camera* cam);
+/* flame_hip_frontend_track with the ingest stage in front: raw = raw_height rows of raw_width pixels of the camera's format,
+ * `pitch` bytes apart (any alignment).  Features, state, counts and info keys are those of _track on the rectified image.
+ * Errors: those of _track; STATE without a camera; ARG when pitch < raw_width x bytes per pixel. */
+int flame_hip_frontend_track_raw(flame_hip_frontend* fe, const flame_hip_frontend_params* params, const uint8_t* raw, int32_t pitch,
+                                 uint32_t img_id, const double T_world_cam[12], int32_t is_poseframe, int32_t* n_out);
+/* The stage alone: out = H rows of W rectified grey bytes, out_pitch (>= W) bytes apart.  Feature state and ring untouched. */
+int flame_hip_frontend_rectify(flame_hip_frontend* fe, const uint8_t* raw, int32_t pitch, uint8_t* out, int32_t out_pitch);
+/* The image the last _track / _track_raw call tracked (after the ingest stage), downloaded; STATE before the first frame. */
+int flame_hip_frontend_image(flame_hip_frontend* fe, uint8_t* out, int32_t out_pitch);
 
 /* Debug/test hook (no device needed; works on a handle created with device = -1): copies the
  * named host-side plan array ("v_o2i", "e_o2i", "grow", "ginc", "eij", "tiles", "t_vmap",

@@ -21,6 +21,9 @@
 // --project-graph: Params::project_graph on (every frame's solve starts from the previous mesh warped into its view).
 // --photo-error: Params::photo_error on; the frame line ends with `photo_total <sum of grey-level errors> photo_avg <per evaluated
 // pixel> photo_pixels <n>` (the frame's filtered map against the last pose frame, every tenth frame here; 0 0 0 before the first).
+// --gpu-rectify (asl): the grey image is loaded unrectified and rectified by the library's ingest stage on the GPU
+// (flame::GpuFrontEnd::setCamera with the dataset's distortion coefficients, GpuFrontEnd::rectify) instead of on the host; the
+// frame lines are the same.  Depth handling is unchanged.
 // --dump dir: frame_<id>.bin = {int32 V, T; float pos[2V], idepth_mu[V], idepth_var[V]; int32 tris[3T]; float idepth[V]}:
 // what went into the regulariser and what came out, for a bit-for-bit comparison with the oracle (tests).
 #include <cmath>
@@ -32,6 +35,7 @@
 #include <vector>
 
 #include "flame/flame.h"
+#include "flame/gpu_frontend.h"
 #include "flame_ros/dataset_streams.h"
 
 namespace ds = flame_ros::datasets;
@@ -137,16 +141,18 @@ struct Lite {
 int main(int argc, char** argv) {
   std::vector<char*> args;
   Lite L;
+  bool gpu_rectify = false;
   for (int k = 1; k < argc; ++k) {
     if (!std::strcmp(argv[k], "--dump") && k + 1 < argc) L.dump_dir = argv[++k];
     else if (!std::strcmp(argv[k], "--project-graph")) L.params.project_graph = true;  // warm-start every frame from the last mesh
     else if (!std::strcmp(argv[k], "--photo-error")) L.params.photo_error = true;      // the evaluate stage behind every frame
+    else if (!std::strcmp(argv[k], "--gpu-rectify")) gpu_rectify = true;               // (asl) undistort on the GPU
     else args.push_back(argv[k]);
   }
   const bool asl = !args.empty() && !std::strcmp(args[0], "asl");
   if (!args.empty() && (!std::strcmp(args[0], "tum") || asl)) args.erase(args.begin());
   if ((asl && args.size() < 4) || (!asl && args.size() < 6)) {
-    std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph] [--photo-error]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph] [--photo-error]\n",
+    std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph] [--photo-error]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-rectify]\n",
                  argv[0], argv[0]);
     return 2;
   }
@@ -164,14 +170,30 @@ int main(int argc, char** argv) {
     const bool distorted = cam.k1 != 0.f || cam.k2 != 0.f || cam.p1 != 0.f || cam.p2 != 0.f || cam.k3 != 0.f;
     uint32_t id = 0;
     ds::AslFrame fr;
+    std::unique_ptr<flame::GpuFrontEnd> ingest;  // --gpu-rectify: the library's ingest stage instead of image_io.h undistort()
     while (data.get(&id, &fr)) {
       std::vector<uint8_t> gray;
       if (!ds::loadFramePixels(fr.rgb_file, fr.has_depth ? fr.depth_file : std::string(), static_cast<float>(data.depthScaleFactor()),
-                               distorted ? &cam : nullptr, false, &L.W, &L.H, &gray, &L.depth, &err)) {
+                               (distorted && !gpu_rectify) ? &cam : nullptr, false, &L.W, &L.H, &gray, &L.depth, &err)) {
         std::fprintf(stderr, "%s\n", err.c_str());
         return 4;
       }
       if (L.W != data.width() || L.H != data.height()) { std::fprintf(stderr, "image size differs from sensor.yaml's resolution\n"); return 4; }
+      if (gpu_rectify) {
+        if (!ingest) {
+          flame::Matrix3f K;
+          for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) K(r, c) = (r == c) ? 1.f : 0.f;
+          K(0, 0) = cam.fx; K(1, 1) = cam.fy; K(0, 2) = cam.cx; K(1, 2) = cam.cy;
+          const float D[5] = {cam.k1, cam.k2, cam.p1, cam.p2, cam.k3};
+          ingest.reset(new flame::GpuFrontEnd(L.W, L.H, K, L.params, 1, 1));
+          if (!ingest->setCamera(L.W, L.H, 1, D)) { std::fprintf(stderr, "--gpu-rectify: hip_error %d\n", ingest->lastError()); return 5; }
+        }
+        flame::Image1b raw(L.H, L.W), rect(L.H, L.W);
+        for (int y = 0; y < L.H; ++y) std::memcpy(raw.ptr<uint8_t>(y), gray.data() + static_cast<size_t>(y) * L.W, L.W);
+        if (!ingest->rectify(raw, &rect)) { std::fprintf(stderr, "--gpu-rectify: hip_error %d\n", ingest->lastError()); return 5; }
+        for (int y = 0; y < L.H; ++y) std::memcpy(gray.data() + static_cast<size_t>(y) * L.W, rect.ptr<uint8_t>(y), L.W);
+      }
       if (!L.sensor) L.construct(cam.fx, cam.fy, cam.cx, cam.cy);
       L.frame(id, fr.time, fr.pose_optical, gray);
     }
