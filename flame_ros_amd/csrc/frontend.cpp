@@ -3,7 +3,9 @@
 // of flame_hip_frontend_track uploads the image, queues kill -> track + project -> (detect) -> assign + compact on the
 // handle's stream and returns when the emitted features are on the host.  Kernels: frontend.hip.  With a camera set
 // (flame_hip_frontend_set_camera) flame_hip_frontend_track_raw puts the ingest stage (ingest.hip: grey, box downsample, undistort)
-// between the upload of the raw image and the tracker, writing into the ring slot the tracker reads.  Reads no environment variable.
+// between the upload of the raw image and the tracker, writing into the ring slot the tracker reads.  flame_hip_frontend_debug_image
+// renders the Detections / Matches picture of the last tracked frame (frontend_debug.hip) from the record the tracker left on the
+// device.  Reads no environment variable.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -60,6 +62,10 @@ struct flame_hip_frontend {
   uint8_t* d_rect = nullptr;
   double ingest_device_us = 0.0;
   int64_t ingest_raw_bytes = 0;
+  // debug images (flame_hip_frontend_debug_image): the rendered picture on the device and its page-locked copy, made at the first call
+  uint8_t* d_dbg = nullptr;
+  uint8_t* h_dbg = nullptr;
+  double debug_image_device_us = 0.0;
 };
 
 namespace {
@@ -96,6 +102,8 @@ void release(flame_hip_frontend* fe) {
     if (fe->d_raw) (void)hipFree(fe->d_raw);
     if (fe->d_scratch) (void)hipFree(fe->d_scratch);
     if (fe->d_rect) (void)hipFree(fe->d_rect);
+    if (fe->d_dbg) (void)hipFree(fe->d_dbg);
+    if (fe->h_dbg) (void)hipHostFree(fe->h_dbg);
     if (fe->evi0) (void)hipEventDestroy(fe->evi0);
     if (fe->evi1) (void)hipEventDestroy(fe->evi1);
     if (fe->ev0) (void)hipEventDestroy(fe->ev0);
@@ -197,7 +205,7 @@ int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, i
     return 0;
   }
   const size_t npix = (size_t)W * H, F = (size_t)max_features;
-  const size_t state_bytes = 12 * ((F * 4 + 255) & ~(size_t)255) + ((F + 255) & ~(size_t)255) + ((F * sizeof(float4) + 255) & ~(size_t)255) +
+  const size_t state_bytes = 13 * ((F * 4 + 255) & ~(size_t)255) + ((F + 255) & ~(size_t)255) + 2 * ((F * sizeof(float4) + 255) & ~(size_t)255) +
                              ((F * sizeof(FeOut) + 255) & ~(size_t)255);
   bool ok = hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&fe->ev0) == hipSuccess &&
             hipEventCreate(&fe->ev1) == hipSuccess && hipEventCreate(&fe->evi0) == hipSuccess && hipEventCreate(&fe->evi1) == hipSuccess;
@@ -222,6 +230,8 @@ int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, i
   f.alive = carve<uint8_t>(p, F);
   f.proj = carve<float4>(p, F);
   f.out = carve<FeOut>(p, F);
+  f.seg = carve<float4>(p, F);
+  f.steps = carve<int32_t>(p, F);
   f.W = W; f.H = H; f.max_features = max_features;
   f.fx = K[0]; f.fy = K[4]; f.cx = K[2]; f.cy = K[5];
   f.imgs = fe->d_imgs;
@@ -483,6 +493,40 @@ int flame_hip_frontend_state(flame_hip_frontend* fe, uint8_t* alive, int32_t* u,
   return 0;
 }
 
+int flame_hip_frontend_searches(flame_hip_frontend* fe, float* seg, int32_t* steps) {
+  if (!fe) return FLAME_HIP_ERR_ARG;
+  if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
+  if (!fe->have_image) return FLAME_HIP_ERR_STATE;
+  FE_HIP(hipSetDevice(fe->device));
+  FE_HIP(hipStreamSynchronize(fe->stream));
+  const size_t F = (size_t)fe->max_features;
+  if (seg) FE_HIP(hipMemcpy(seg, fe->fr.seg, 16 * F, hipMemcpyDeviceToHost));
+  if (steps) FE_HIP(hipMemcpy(steps, fe->fr.steps, 4 * F, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int flame_hip_frontend_debug_image(flame_hip_frontend* fe, int32_t kind, uint8_t* bgr, int32_t pitch) {
+  if (!fe || !bgr || (kind != FLAME_HIP_FE_IMG_DETECTIONS && kind != FLAME_HIP_FE_IMG_MATCHES) || pitch < 3 * fe->W) return FLAME_HIP_ERR_ARG;
+  if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
+  if (!fe->have_image) return FLAME_HIP_ERR_STATE;
+  FE_HIP(hipSetDevice(fe->device));
+  const size_t row = 3 * (size_t)fe->W, bytes = row * fe->H;
+  if (!fe->d_dbg && hipMalloc(&fe->d_dbg, bytes) != hipSuccess) return FLAME_HIP_ERR_ALLOC;
+  if (!fe->h_dbg && hipHostMalloc(&fe->h_dbg, bytes) != hipSuccess) return FLAME_HIP_ERR_ALLOC;
+  hipStream_t s = fe->stream;
+  FE_HIP(hipEventRecord(fe->ev0, s));
+  if (kind == FLAME_HIP_FE_IMG_MATCHES) fe_launch_debug_matches(s, fe->fr, fe->d_dbg);
+  else fe_launch_debug_detections(s, fe->fr, fe->n_out, fe->d_dbg);
+  FE_HIP(hipGetLastError());
+  FE_HIP(hipEventRecord(fe->ev1, s));
+  FE_HIP(hipMemcpyAsync(fe->h_dbg, fe->d_dbg, bytes, hipMemcpyDeviceToHost, s));
+  FE_HIP(hipStreamSynchronize(s));
+  for (int32_t y = 0; y < fe->H; ++y) std::memcpy(bgr + (size_t)y * pitch, fe->h_dbg + (size_t)y * row, row);
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, fe->ev0, fe->ev1) == hipSuccess) fe->debug_image_device_us = 1000.0 * ms;
+  return 0;
+}
+
 int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value) {
   if (!fe || !key || !value) return FLAME_HIP_ERR_ARG;
   static const char* const kStatus[] = {"ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died"};
@@ -495,6 +539,7 @@ int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* va
   if (!std::strcmp(key, "max_features")) { *value = fe->max_features; return 0; }
   if (!std::strcmp(key, "ingest_device_us")) { *value = (int64_t)(fe->ingest_device_us + 0.5); return 0; }
   if (!std::strcmp(key, "ingest_raw_bytes")) { *value = fe->ingest_raw_bytes; return 0; }
+  if (!std::strcmp(key, "debug_image_device_us")) { *value = (int64_t)(fe->debug_image_device_us + 0.5); return 0; }
   if (!std::strcmp(key, "camera")) { *value = fe->have_cam ? 1 : 0; return 0; }
   if (!std::strcmp(key, "poseframes")) {
     int64_t c = 0;

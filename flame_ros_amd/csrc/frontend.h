@@ -76,11 +76,19 @@ struct FeFrame {
   int32_t* freelist;             // max_features
   FeOut* out;                    // max_features
   int32_t* counts;               // kFeCounts
+  // the search record of the frame (debug images, flame_hip_frontend_searches): zero for a slot that ran no search
+  float4* seg;     // {x0, y0, ex, ey}: sample k of the search sits at (x0 + k ex, y0 + k ey)
+  int32_t* steps;  // S (0 = no search ran: free, NO_PARALLAX, OUTSIDE before the segment exists, NEW)
 };
 
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask);
 void fe_launch_track(hipStream_t s, const FeFrame& f);
 void fe_launch_detect(hipStream_t s, const FeFrame& f);
 void fe_launch_compact(hipStream_t s, const FeFrame& f);
+
+// frontend_debug.hip: the Detections / Matches debug images (DESIGN.md 5.3 "Debug images"), BGR8 with dense rows (3 W bytes) into
+// `bgr`, from the frame's record in `f` (status, kstar, seg, steps; the first n_out records of f.out) on stream s.
+void fe_launch_debug_matches(hipStream_t s, const FeFrame& f, uint8_t* bgr);
+void fe_launch_debug_detections(hipStream_t s, const FeFrame& f, int32_t n_out, uint8_t* bgr);
 
 }  // namespace flamehip

@@ -81,6 +81,8 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
       f.status[slot] = kFeFree;
       f.kstar[slot] = -1;
       f.cell_of[slot] = -1;
+      f.seg[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      f.steps[slot] = 0;
     }
     return;
   }
@@ -105,6 +107,8 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
 
   int status, ks = -1;
   float mu_new = mu, var_new = var;
+  float4 seg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the search record: stays zero when no search runs
+  int steps = 0;
   if (!(d0 > 0.0f && d1 > 0.0f) || !ref_in) {
     status = kFeOutside;  // an end of the search lies behind the camera / the reference patch leaves its image
   } else {
@@ -117,6 +121,8 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
     } else {
       const int S = L >= (float)kFeMaxSamples ? kFeMaxSamples : (int)ceilf(L);
       const float ex = dx / (float)S, ey = dy / (float)S;
+      seg = make_float4(x0, y0, ex, ey);
+      steps = S;
       unsigned long long C[kFePasses];
       unsigned long long best = kNone;
 #pragma unroll
@@ -229,6 +235,8 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
     f.var[slot] = var;
     f.drop[slot] = drop;
     f.kstar[slot] = ks;
+    f.seg[slot] = seg;
+    f.steps[slot] = steps;
     atomicAdd(&f.counts[2 + status], 1);
     if (dies) {
       f.alive[slot] = 0;
@@ -332,6 +340,8 @@ __global__ __launch_bounds__(1024) void k_fe_compact(FeFrame f) {
         f.var[slot] = f.var_init;
         f.status[slot] = kFeNew;
         f.kstar[slot] = -1;
+        f.seg[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (the slot may have died in this very frame: its search goes with it)
+        f.steps[slot] = 0;
         f.cell_of[slot] = cell;
         f.proj[slot] = make_float4((float)x, (float)y, f.idepth_init, f.var_init);
         f.cell_key[cell] = ((unsigned long long)__float_as_uint(f.var_init) << 32) | (unsigned long long)(unsigned int)slot;

@@ -13,6 +13,7 @@ from .lib import FlameHipError  # noqa: F401
 
 FE_OK, FE_NO_PARALLAX, FE_OUTSIDE, FE_BAD_MATCH, FE_AMBIGUOUS, FE_NEW, FE_DIED, FE_FREE = 0, 1, 2, 3, 4, 5, 6, -1
 STATUS_KEYS = ("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died")
+IMG_DETECTIONS, IMG_MATCHES = _l.FE_IMG_DETECTIONS, _l.FE_IMG_MATCHES  # FLAME_HIP_FE_IMG_*
 PIX_CHANNELS = {_l.PIX_GRAY8: 1, _l.PIX_BGR8: 3, _l.PIX_RGB8: 3, _l.PIX_BGRA8: 4, _l.PIX_RGBA8: 4}
 
 
@@ -139,6 +140,25 @@ class GpuFrontEnd:
         out = np.zeros((self.H, self.W), np.uint8)
         _l.check(self._lib.flame_hip_frontend_image(self._h, _ptr(out), self.W), "flame_hip_frontend_image")
         return out
+
+    def debug_image(self, kind, pitch=None, out=None):
+        """The Detections / Matches debug image (IMG_*) of the last tracked frame, rendered on the GPU: (H, W, 3) uint8, BGR.
+        `pitch`: bytes between rows (>= 3 W); `out`: a flat uint8 buffer of H x pitch bytes to draw into (the result is a view of
+        it; the bytes between the rows are left alone)."""
+        pitch = 3 * self.W if pitch is None else int(pitch)
+        if out is None:
+            out = np.zeros(self.H * max(pitch, 0), np.uint8)
+        if out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous or out.size < self.H * pitch:
+            raise ValueError("out must be a flat uint8 buffer of H x pitch bytes")
+        _l.check(self._lib.flame_hip_frontend_debug_image(self._h, int(kind), _ptr(out), pitch), "flame_hip_frontend_debug_image")
+        return np.lib.stride_tricks.as_strided(out, (self.H, self.W, 3), (pitch, 3, 1))
+
+    def searches(self):
+        """The search every slot ran in the last frame (debug hook): seg (F, 4) = {x0, y0, ex, ey}, steps (F,) = S, 0 = none."""
+        F = self.max_features
+        s = dict(seg=np.zeros((F, 4), np.float32), steps=np.zeros(F, np.int32))
+        _l.check(self._lib.flame_hip_frontend_searches(self._h, _ptr(s["seg"]), _ptr(s["steps"])), "flame_hip_frontend_searches")
+        return s
 
     def features(self, n=None):
         n = self.info("emitted") if n is None else n

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("FLAME_HIP_LIB") or os.path.join(HERE, "libflame_hip.s
 ERR_ARG, ERR_STATE, ERR_NAN, ERR_ALLOC, ERR_NODEVICE, ERR_NORCCL, ERR_HIP, ERR_RCCL = -1, -2, -3, -4, -5, -6, -1000, -3000
 PATH_AUTO, PATH_GLOBAL, PATH_TILE = 0, 1, 2
 IMG_WIREFRAME, IMG_FEATURES, IMG_NORMALS, IMG_IDEPTHMAP = 0, 1, 2, 3
+FE_IMG_DETECTIONS, FE_IMG_MATCHES = 0, 1  # flame_hip_frontend_debug_image (frontend.py: IMG_DETECTIONS, IMG_MATCHES)
 PIX_GRAY8, PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8 = 0, 1, 2, 3, 4
 
 
@@ -127,6 +128,8 @@ SYMBOLS = {
     "flame_hip_frontend_track_raw": (C.c_int, [_VP, _VP, _VP, _I32, C.c_uint32, _VP, _I32, C.POINTER(_I32)]),
     "flame_hip_frontend_rectify": (C.c_int, [_VP, _VP, _I32, _VP, _I32]),
     "flame_hip_frontend_image": (C.c_int, [_VP, _VP, _I32]),
+    "flame_hip_frontend_searches": (C.c_int, [_VP, _VP, _VP]),
+    "flame_hip_frontend_debug_image": (C.c_int, [_VP, _I32, _VP, _I32]),
     "flame_hip_debug_plan_array": (_I64, [_VP, C.c_char_p, _VP, _I64]),
     "flame_hip_strerror": (C.c_char_p, [C.c_int]),
     "flame_hip_version": (C.c_int, []),

@@ -85,6 +85,10 @@ struct FrontEnd {
   // and rectifies them itself, GpuFrontEnd::setCamera; called after a successful `track`, under the mutex update() holds, by
   // the stages that read pixels -- the evaluate stage; nullptr = not available, which fails that stage)
   std::function<const Image1b*()> rectified;
+  // the feature pipeline's own debug images (optional): `kind` = FLAME_HIP_FE_IMG_DETECTIONS / _MATCHES, `*out` becomes the
+  // width x height BGR8 picture of the last frame `track` tracked; false = not available.  Called by getDebugImageDetections() /
+  // getDebugImageMatches(), under the mutex update() holds, at most once per tracked frame and kind.
+  std::function<bool(int kind, Image3b* out)> debugImage;
 };
 
 // Ground-truth statistics of the committed frame's filtered dense idepth map (Flame::getTruthStats): the confusion matrix and
@@ -106,8 +110,8 @@ class Flame {
     const Vec3b black(0, 0, 0);
     debug_wireframe_.img = Image3b(height, width, black);
     debug_features_.img = Image3b(height, width, black);
-    debug_detections_ = Image3b(height, width, black);
-    debug_matches_ = Image3b(height, width, black);
+    debug_detections_.img = Image3b(height, width, black);
+    debug_matches_.img = Image3b(height, width, black);
     debug_normals_.img = Image3b(height, width, black);
     debug_idepthmap_.img = Image3b(height, width, black);
   }
@@ -248,18 +252,27 @@ class Flame {
   // (the input image is not kept).  They are rendered ON THE GPU (flame_hip_debug_image) and only
   // when a getter asks: update() itself draws nothing -- the first call of a getter after an
   // update renders that image from the frame's device state and copies it out, later calls return
-  // the cached image.  A disabled image (Params::debug_draw_*) stays black.  Detections / Matches
-  // belong to the feature pipeline: black images of the right size.  debug_flip_images rotates the
-  // rendered images by 180 degrees (cfg/flame_offline_tum.yaml:65); debug_draw_text_overlay is not
-  // applied (no font rendering here).
+  // the cached image.  A disabled image (Params::debug_draw_*) stays black.  Detections ("feature
+  // detections") / Matches ("epipolar line searches (green success, red failure)") belong to the
+  // feature pipeline: they come from FrontEnd::debugImage (GpuFrontEnd renders them on the GPU over
+  // the tracked grey image; flame_hip.h, flame_hip_frontend_debug_image) under the same discipline,
+  // and show the last frame the front end TRACKED, whatever became of that update -- a frame that
+  // failed at the variance gate is the one to look at.  Without that callback, with the flag off
+  // (both default to false) or before an update() has called `track` they are black images of the
+  // right size.  debug_flip_images rotates the rendered images by 180 degrees
+  // (cfg/flame_offline_tum.yaml:65); debug_draw_text_overlay is not applied (no font rendering here).
   const Image3b& getDebugImageWireframe() const {
     return debugImage(FLAME_HIP_IMG_WIREFRAME, params_.debug_draw_wireframe, &debug_wireframe_);
   }
   const Image3b& getDebugImageFeatures() const {
     return debugImage(FLAME_HIP_IMG_FEATURES, params_.debug_draw_features, &debug_features_);
   }
-  const Image3b& getDebugImageDetections() const { return debug_detections_; }
-  const Image3b& getDebugImageMatches() const { return debug_matches_; }
+  const Image3b& getDebugImageDetections() const {
+    return frontEndImage(FLAME_HIP_FE_IMG_DETECTIONS, params_.debug_draw_detections, &debug_detections_);
+  }
+  const Image3b& getDebugImageMatches() const {
+    return frontEndImage(FLAME_HIP_FE_IMG_MATCHES, params_.debug_draw_matches, &debug_matches_);
+  }
   const Image3b& getDebugImageNormals() const {
     return debugImage(FLAME_HIP_IMG_NORMALS, params_.debug_draw_normals, &debug_normals_);
   }
@@ -295,6 +308,7 @@ class Flame {
     } else {
       FeatureSet fs;
       stats_.tick("update_idepths");
+      ++track_serial_;  // the front end's debug images of earlier frames are stale (rendered on demand, see frontEndImage)
       ok = frontend_.track(in, &fs) && fs.idepth_mu.size() == fs.vtx.size() &&
            fs.idepth_var.size() == fs.vtx.size() &&
            (fs.prediction.empty() || fs.prediction.size() == fs.vtx.size());
@@ -629,6 +643,12 @@ class Flame {
                               feats ? static_cast<int32_t>(raw_vtx_.size()) : 0, feats ? dbg_fpos_.data() : nullptr,
                               feats ? raw_mu_.data() : nullptr, dbg_buf_.data()))
       return d->img;  // the previous image stays
+    commitDebugImage(d);
+    d->serial = frame_serial_;
+    return d->img;
+  }
+  // dbg_buf_ (dense BGR8) into d->img, rotated by 180 degrees under debug_flip_images
+  void commitDebugImage(DebugImage* d) const {
     static_assert(sizeof(Vec3b) == 3, "BGR8 pixels are packed");
     if (params_.debug_flip_images) {  // "Rotated debug images by 180 degrees for display" (yaml :65)
       uint8_t* b = dbg_buf_.data();
@@ -639,7 +659,21 @@ class Flame {
     for (int i = 0; i < height_; ++i)  // rows of both image types are contiguous
       std::memcpy(static_cast<void*>(&d->img(i, 0)), dbg_buf_.data() + 3 * static_cast<size_t>(i) * width_,
                   3 * static_cast<size_t>(width_));
-    d->serial = frame_serial_;
+  }
+  // Detections / Matches: rendered by the front end (FrontEnd::debugImage) for the last frame it tracked, at the first call of
+  // the getter after that frame; `serial` is then the track_serial_ the image belongs to.
+  const Image3b& frontEndImage(int kind, bool enabled, DebugImage* d) const {
+    std::lock_guard<std::mutex> lock(mtx_);
+    if (!enabled || !frontend_.debugImage || track_serial_ == 0 || d->serial == track_serial_) return d->img;
+    if (fe_dbg_img_.rows != height_ || fe_dbg_img_.cols != width_) fe_dbg_img_ = Image3b(height_, width_);
+    if (!frontend_.debugImage(kind, &fe_dbg_img_) || fe_dbg_img_.rows != height_ || fe_dbg_img_.cols != width_)
+      return d->img;  // the previous image stays
+    dbg_buf_.resize(3 * static_cast<size_t>(width_) * height_);
+    for (int i = 0; i < height_; ++i)
+      std::memcpy(dbg_buf_.data() + 3 * static_cast<size_t>(i) * width_, static_cast<const void*>(&fe_dbg_img_(i, 0)),
+                  3 * static_cast<size_t>(width_));
+    commitDebugImage(d);
+    d->serial = track_serial_;
     return d->img;
   }
 
@@ -671,7 +705,9 @@ class Flame {
   std::vector<Edge> st_edges_;
   std::vector<uint8_t> st_tri_valid_;
   uint64_t frame_serial_ = 0;        // successful updates so far
-  Image3b debug_detections_, debug_matches_;
+  uint64_t track_serial_ = 0;        // update() calls that reached the front end's `track` so far
+  mutable DebugImage debug_detections_, debug_matches_;  // (serial: track_serial_)
+  mutable Image3b fe_dbg_img_;       // what FrontEnd::debugImage renders into
   mutable DebugImage debug_wireframe_, debug_features_, debug_normals_, debug_idepthmap_;
   mutable std::vector<uint8_t> dbg_buf_;
   mutable std::vector<float> dbg_fpos_;

@@ -6,8 +6,9 @@
 //   sensor.setFrontEnd(features.frontEnd());
 //   sensor.update(time, img_id, pose, gray, is_poseframe);   // reference src/flame_offline_tum.cc:578-579
 //
-// frontEnd() binds `track`, `updatePoseFramePoses`, `prunePoseFrames` and `reportStats` (the tracking stat keys num_idepth_updates
-// / num_fail_*) to this object (which must outlive the Flame it feeds); `triangulate` stays empty, so the library's GPU Delaunay triangulation runs.  `track` hands every emitted feature of the frame
+// frontEnd() binds `track`, `updatePoseFramePoses`, `prunePoseFrames`, `reportStats` (the tracking stat keys num_idepth_updates
+// / num_fail_*) and `debugImage` (the Detections / Matches pictures behind Flame::getDebugImageDetections() / ...Matches(), drawn
+// on the GPU when Params::debug_draw_detections / debug_draw_matches ask for them) to this object (which must outlive the Flame it feeds); `triangulate` stays empty, so the library's GPU Delaunay triangulation runs.  `track` hands every emitted feature of the frame
 // to Flame (whose variance gate selects the ones that enter the graph) and fails the frame when fewer than three are emitted.
 // Poses are T_world_cam; they cross into the library as row-major [R|t] in double, made from the unit quaternion and the
 // translation of SE3f (Sophus::SE3f when present, the fallback struct otherwise).  Nothing throws; a failure leaves its code
@@ -63,6 +64,7 @@ class GpuFrontEnd {
     fe.prunePoseFrames = [this](const std::vector<uint32_t>& ids) { prunePoseFrames(ids); };
     fe.reportStats = [this](utils::StatsTracker* stats) { reportStats(stats); };
     if (have_camera_) fe.rectified = [this]() { return rectified(); };
+    fe.debugImage = [this](int kind, Image3b* out) { return debugImage(kind, out); };
     return fe;
   }
 
@@ -105,6 +107,19 @@ class GpuFrontEnd {
       rectified_valid_ = true;
     }
     return &rectified_;
+  }
+
+  // The Detections / Matches debug image (FLAME_HIP_FE_IMG_*; flame_hip.h, flame_hip_frontend_debug_image) of the last frame
+  // track() tracked, rendered on the GPU: `*out` becomes width x height BGR8.  false (lastError()) before the first frame.
+  bool debugImage(int kind, Image3b* out) {
+    if (!handle_) return false;
+    if (!out) return fail(FLAME_HIP_ERR_ARG);
+    if (out->rows != height_ || out->cols != width_) *out = Image3b(height_, width_);
+    static_assert(sizeof(Vec3b) == 3, "BGR8 pixels are packed");
+    const int32_t pitch = height_ > 1 ? static_cast<int32_t>(out->ptr<uint8_t>(1) - out->ptr<uint8_t>(0)) : 3 * width_;
+    const int rc = flame_hip_frontend_debug_image(handle_, kind, out->ptr<uint8_t>(0), pitch);
+    if (rc) return fail(rc);
+    return true;
   }
 
   bool track(const FrameInput& in, FeatureSet* out) {

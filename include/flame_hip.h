@@ -523,7 +523,7 @@ enum {
 void flame_hip_frontend_default_params(flame_hip_frontend_params* p);
 /* K row-major 3x3 pinhole (fx = K[0], fy = K[4], cx = K[2], cy = K[5]); images arrive rectified unless a camera is set
  * (flame_hip_frontend_set_camera below).  8 <= W, H <= 8192; max_poseframes <= 64.  Device memory: (max_poseframes + 1) W H
- * bytes + ~100 bytes per feature slot.  device = -1 makes a handle without a device: arguments are checked as usual and every
+ * bytes + ~120 bytes per feature slot (+ 3 W H bytes once a debug image is asked for).  device = -1 makes a handle without a device: arguments are checked as usual and every
  * call that needs the device returns NODEVICE. */
 int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, int32_t H, const float K[9], int32_t max_features,
                               int32_t max_poseframes);
@@ -554,6 +554,34 @@ int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* va
  * ring slot of its pose frame, prior (mu, var) in the pose frame, dropout counter, last status (-1 = free), last best sample. */
 int flame_hip_frontend_state(flame_hip_frontend* fe, uint8_t* alive, int32_t* u, int32_t* v, int32_t* poseframe, float* mu, float* var,
                              int32_t* dropouts, int32_t* status, int32_t* kstar);
+/* Debug/test hook: the search every slot ran in the last frame (max_features entries each; any pointer may be NULL):
+ * seg = {x0, y0, ex, ey} per slot (sample k of the search sits at (x0 + k ex, y0 + k ey)), steps = S (0 = no search ran).
+ * steps is 0, and seg all zero, for a free slot, NO_PARALLAX, OUTSIDE decided before the segment exists and a slot a NEW feature
+ * took in this frame.  Errors: ARG (NULL fe), NODEVICE, STATE before the first tracked frame. */
+int flame_hip_frontend_searches(flame_hip_frontend* fe, float* seg, int32_t* steps);
+
+/* ---- the feature pipeline's two debug images (reference cfg/flame_offline_tum.yaml:60-61: "feature detections", "epipolar line
+ * searches (green success, red failure)"), rendered on the device from the record of the last tracked frame.  Integer pictures;
+ * tests/fe_debug_ref.py restates the rules below and the GPU equals it byte for byte (DESIGN.md 5.3 "Debug images").
+ *   Background (both): pixel (x, y) = (g, g, g), g = the tracked grey image (what flame_hip_frontend_image returns).
+ *   MATCHES: a slot draws iff its status of the last frame is OK, OUTSIDE, BAD_MATCH, AMBIGUOUS or DIED and steps > 0 (alive is
+ *     not consulted; a slot that died and was taken by a detection in the same frame is NEW and draws nothing).  Sample k = 0..S
+ *     sits at px = x0 + (float)k ex, py = y0 + (float)k ey (float32, each operation rounded on its own, no fused multiply-add:
+ *     the tracker's expression, the same bits); its pixel is X = floorf(px + 0.5f), Y = floorf(py + 0.5f), drawn only when
+ *     0 <= X <= W - 1 and 0 <= Y <= H - 1, tested in float before the conversion (a NaN or infinite position draws nothing).
+ *     Layer 1: every sample pixel of an OK slot, (B, G, R) = (0, 255, 0); layer 2: every sample pixel of a slot with any other
+ *     drawing status, (0, 0, 255); layer 3: the pixel of sample k* of an OK slot, (0, 255, 255).  A pixel shows its highest
+ *     layer, else the background.  (At the 256-step cap the samples are more than a pixel apart: the line is dotted.)
+ *   DETECTIONS: every emitted feature (what flame_hip_frontend_features returns) gives a 3 x 3 filled square centred at
+ *     (floorf(x + 0.5f), floorf(y + 0.5f)), clipped to the image: layer 2, (0, 255, 0), for status NEW; layer 1, (255, 0, 0), for
+ *     every other emitted feature (the ones that occupy a cell, which therefore got no detection).  Highest layer wins.
+ * The colour depends on the layer alone, so nothing depends on the order slots, samples or lanes arrive in. */
+enum { FLAME_HIP_FE_IMG_DETECTIONS = 0, FLAME_HIP_FE_IMG_MATCHES = 1 };
+/* BGR8, W x H, rows `pitch` (>= 3 W) bytes apart (bytes between the rows are left alone), of the frame the last _track / _track_raw
+ * call tracked.  Rendered on the device on the front end's stream from that frame's record; set_poses / prune in between do not
+ * change it.  Synchronises.  Info key "debug_image_device_us": HIP events around the last render.  Errors: ARG (NULL fe or bgr,
+ * unknown kind, pitch < 3 W), NODEVICE (after the argument checks), STATE before the first tracked frame. */
+int flame_hip_frontend_debug_image(flame_hip_frontend* fe, int32_t kind, uint8_t* bgr, int32_t pitch);
 
 /* ---- ingest stage (opt-in): raw camera images in front of the tracker.  With a camera set, _track_raw takes the image as the
  * camera delivers it and runs three steps on the handle's stream between the upload and the tracker, each rounded to uint8

@@ -7,14 +7,15 @@
 // dataset index -> image files -> pixels (include/flame_ros/dataset_streams.h, image_io.h) -> flame::Flame::update()
 // with a registered FrontEnd -> idepth mesh + stats per frame.
 //
-// The feature pipeline (detection, epipolar tracking) plugs in through flame::FrontEnd; this tool does not use the GPU
-// one (flame/gpu_frontend.h) yet.  The stand-in used here is deliberately simple and says so: one feature per detection_win_size
-// cell (cfg/flame_offline_tum.yaml:78) where the dataset's DEPTH image is valid, idepth = 1 / depth at that pixel
-// (what analysis/pass_in_truth feeds, src/flame_offline_tum.cc:577-595).  The kept features are triangulated by the
-// facade's built-in Delaunay triangulator (flame/utils/delaunay.h); everything behind the FrontEnd is the product path.
+// The feature pipeline (detection, epipolar tracking) plugs in through flame::FrontEnd.  With --gpu-frontend it is the GPU one
+// (flame/gpu_frontend.h: image -> GPU tracker -> mesh, the depth image only scores the result).  Without the flag it is a stand-in
+// that is deliberately simple and says so: one feature per detection_win_size cell (cfg/flame_offline_tum.yaml:78) where the
+// dataset's DEPTH image is valid, idepth = 1 / depth at that pixel (what analysis/pass_in_truth feeds,
+// src/flame_offline_tum.cc:577-595).  The kept features are triangulated by the library; everything behind the FrontEnd is the
+// product path.
 //
-//   flame_offline_lite [tum] <index.txt> <frame RDF|FLU|...> fx fy cx cy [iters] [--dump dir]
-//   flame_offline_lite asl <pose_dir> <rgb_dir> <depth_dir> <world frame RDF|FLU|FRD|RFU> [iters] [--dump dir]
+//   flame_offline_lite [tum] <index.txt> <frame RDF|FLU|...> fx fy cx cy [iters] [options]
+//   flame_offline_lite asl <pose_dir> <rgb_dir> <depth_dir> <world frame RDF|FLU|FRD|RFU> [iters] [options]
 //     (K, the distortion coefficients and the depth scale come from the sensor.yaml files, as in the reference)
 // -> one line per frame:
 //   frame <id> time <t> ok <0|1> feats <n> vtx <n> tris <n> edges <n> coverage <c> cost_smooth <s> cost_data <d> rms_vs_truth <r> update_ms <ms> ...
@@ -24,6 +25,13 @@
 // --gpu-rectify (asl): the grey image is loaded unrectified and rectified by the library's ingest stage on the GPU
 // (flame::GpuFrontEnd::setCamera with the dataset's distortion coefficients, GpuFrontEnd::rectify) instead of on the host; the
 // frame lines are the same.  Depth handling is unchanged.
+// --gpu-frontend: the features come from a flame::GpuFrontEnd (detection + epipolar tracking on the GPU) instead of the depth
+// stand-in; the depth image, where present, is used only for rms_vs_truth.  Pose frames stay (id % 10) == 0; the frame line keeps
+// its fields (feats = the features the tracker emitted, also on a frame that failed).  The first frames of a sequence fail --
+// nothing has passed the variance gate yet -- so the exit code is 3.  In asl mode together with --gpu-rectify the one GpuFrontEnd
+// gets setCamera and takes the raw image: no separate rectify call, no host undistortion.  Not together with --dump.
+// --debug-images dir (needs --gpu-frontend): Params::debug_draw_detections / debug_draw_matches on; after every frame
+// dir/detections_<id>.ppm and dir/matches_<id>.ppm (binary P6, RGB) from getDebugImageDetections() / getDebugImageMatches().
 // --dump dir: frame_<id>.bin = {int32 V, T; float pos[2V], idepth_mu[V], idepth_var[V]; int32 tris[3T]; float idepth[V]}:
 // what went into the regulariser and what came out, for a bit-for-bit comparison with the oracle (tests).
 #include <cmath>
@@ -54,8 +62,12 @@ struct Lite {
   std::vector<float> depth;  // the current frame's depth image in metres (shared with the front end)
   std::vector<float> fmu, fvar;  // the features of the current frame as the front end handed them over
   int W = 0, H = 0;
-  std::string dump_dir;
+  std::string dump_dir, debug_dir;
   int failed = 0;
+  bool gpu_frontend = false;
+  std::unique_ptr<flame::GpuFrontEnd> gpu;  // --gpu-frontend: the feature pipeline
+  bool raw_camera = false;                  // ... which takes raw images and rectifies them itself (asl --gpu-rectify)
+  float D[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 
   flame::FrontEnd frontEnd() {
     flame::FrontEnd fe;
@@ -83,7 +95,26 @@ struct Lite {
     Kinv(0, 0) = 1.f / fx; Kinv(0, 1) = 0.f; Kinv(0, 2) = -cx / fx; Kinv(1, 0) = 0.f; Kinv(1, 1) = 1.f / fy; Kinv(1, 2) = -cy / fy;
     Kinv(2, 0) = 0.f; Kinv(2, 1) = 0.f; Kinv(2, 2) = 1.f;
     sensor = std::make_shared<flame::Flame>(W, H, K, Kinv, params);
-    sensor->setFrontEnd(frontEnd());
+    if (gpu_frontend) {
+      gpu.reset(new flame::GpuFrontEnd(W, H, K, params));
+      if (raw_camera && !gpu->setCamera(W, H, 1, D)) std::fprintf(stderr, "--gpu-rectify: hip_error %d\n", gpu->lastError());
+      sensor->setFrontEnd(gpu->frontEnd());
+    } else {
+      sensor->setFrontEnd(frontEnd());
+    }
+  }
+
+  static void writePpm(const std::string& path, const flame::Image3b& bgr) {
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return; }
+    std::fprintf(f, "P6\n%d %d\n255\n", bgr.cols, bgr.rows);
+    std::vector<uint8_t> row(3 * static_cast<size_t>(bgr.cols));
+    for (int y = 0; y < bgr.rows; ++y) {
+      for (int x = 0; x < bgr.cols; ++x)
+        for (int c = 0; c < 3; ++c) row[3 * static_cast<size_t>(x) + c] = bgr(y, x)[2 - c];
+      std::fwrite(row.data(), 1, row.size(), f);
+    }
+    std::fclose(f);
   }
 
   // one frame: pose in DOUBLE precision as the dataset streams deliver it, cast to float where the reference
@@ -106,7 +137,7 @@ struct Lite {
     sensor->getInverseDepthMesh(&vtx, &idepths, &normals, &tris, &valid, &edges);
     double se = 0.0;
     size_t n = 0;
-    for (size_t v = 0; ok && v < vtx.size(); ++v) {
+    for (size_t v = 0; ok && !depth.empty() && v < vtx.size(); ++v) {
       const float d = depth[static_cast<size_t>(vtx[v].y) * W + static_cast<size_t>(vtx[v].x)];
       if (d > 0.f) { const double e = idepths[v] - 1.0 / d; se += e * e; ++n; }
     }
@@ -124,8 +155,18 @@ struct Lite {
       }
     }
     const flame::utils::StatsTracker& st = sensor->stats();
+    int feats = static_cast<int>(st.stats("num_feats"));
+    if (gpu) {  // what the tracker emitted for THIS frame (num_feats is the last committed frame's)
+      int64_t emitted = 0;
+      if (gpu->handle() && flame_hip_frontend_info(gpu->handle(), "emitted", &emitted) == 0) feats = static_cast<int>(emitted);
+      else feats = 0;
+    }
+    if (!debug_dir.empty()) {
+      writePpm(debug_dir + "/detections_" + std::to_string(id) + ".ppm", sensor->getDebugImageDetections());
+      writePpm(debug_dir + "/matches_" + std::to_string(id) + ".ppm", sensor->getDebugImageMatches());
+    }
     std::printf("frame %u time %.6f ok %d feats %d vtx %zu tris %zu edges %zu coverage %.4f cost_smooth %.6g cost_data %.6g rms_vs_truth %.6g update_ms %.3f hip_error %d persist_used %d pose_t %.9g %.9g %.9g pose_q %.9g %.9g %.9g %.9g",
-                id, time, ok ? 1 : 0, static_cast<int>(st.stats("num_feats")), vtx.size(), tris.size(), edges.size(),
+                id, time, ok ? 1 : 0, feats, vtx.size(), tris.size(), edges.size(),
                 st.stats("coverage"), st.stats("nltgv2_total_smoothness_cost"), st.stats("nltgv2_total_data_cost"),
                 n ? std::sqrt(se / n) : 0.0, st.timings("update"), static_cast<int>(st.stats("hip_error")),
                 static_cast<int>(st.stats("persist_used")), pose.t[0], pose.t[1], pose.t[2], pose.q[0], pose.q[1], pose.q[2], pose.q[3]);
@@ -147,15 +188,20 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[k], "--project-graph")) L.params.project_graph = true;  // warm-start every frame from the last mesh
     else if (!std::strcmp(argv[k], "--photo-error")) L.params.photo_error = true;      // the evaluate stage behind every frame
     else if (!std::strcmp(argv[k], "--gpu-rectify")) gpu_rectify = true;               // (asl) undistort on the GPU
+    else if (!std::strcmp(argv[k], "--gpu-frontend")) L.gpu_frontend = true;           // features from flame::GpuFrontEnd
+    else if (!std::strcmp(argv[k], "--debug-images") && k + 1 < argc) L.debug_dir = argv[++k];
     else args.push_back(argv[k]);
   }
   const bool asl = !args.empty() && !std::strcmp(args[0], "asl");
   if (!args.empty() && (!std::strcmp(args[0], "tum") || asl)) args.erase(args.begin());
-  if ((asl && args.size() < 4) || (!asl && args.size() < 6)) {
-    std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph] [--photo-error]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-rectify]\n",
+  const bool bad_flags = (!L.debug_dir.empty() && !L.gpu_frontend) || (!L.dump_dir.empty() && L.gpu_frontend);
+  if (bad_flags || (asl && args.size() < 4) || (!asl && args.size() < 6)) {
+    std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-frontend [--debug-images dir]]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-rectify] [--gpu-frontend [--debug-images dir]]\n"
+                 "  --gpu-frontend: features from the GPU tracker (not with --dump); --debug-images dir: detections_<id>.ppm / matches_<id>.ppm per frame (needs --gpu-frontend)\n",
                  argv[0], argv[0]);
     return 2;
   }
+  if (!L.debug_dir.empty()) L.params.debug_draw_detections = L.params.debug_draw_matches = true;
   std::string err;
   if (asl) {
     // ---- flame_offline_asl: K / D / depth scale from the sensor.yaml files, colour image rectified, depth not ----
@@ -168,6 +214,11 @@ int main(int argc, char** argv) {
     cam.k1 = static_cast<float>(data.D()[0]); cam.k2 = static_cast<float>(data.D()[1]);
     cam.p1 = static_cast<float>(data.D()[2]); cam.p2 = static_cast<float>(data.D()[3]); cam.k3 = static_cast<float>(data.D()[4]);
     const bool distorted = cam.k1 != 0.f || cam.k2 != 0.f || cam.p1 != 0.f || cam.p2 != 0.f || cam.k3 != 0.f;
+    if (gpu_rectify && L.gpu_frontend) {  // the one GpuFrontEnd takes the raw image (construct(): setCamera)
+      L.raw_camera = true;
+      const float D[5] = {cam.k1, cam.k2, cam.p1, cam.p2, cam.k3};
+      std::memcpy(L.D, D, sizeof(D));
+    }
     uint32_t id = 0;
     ds::AslFrame fr;
     std::unique_ptr<flame::GpuFrontEnd> ingest;  // --gpu-rectify: the library's ingest stage instead of image_io.h undistort()
@@ -179,7 +230,7 @@ int main(int argc, char** argv) {
         return 4;
       }
       if (L.W != data.width() || L.H != data.height()) { std::fprintf(stderr, "image size differs from sensor.yaml's resolution\n"); return 4; }
-      if (gpu_rectify) {
+      if (gpu_rectify && !L.gpu_frontend) {
         if (!ingest) {
           flame::Matrix3f K;
           for (int r = 0; r < 3; ++r)
