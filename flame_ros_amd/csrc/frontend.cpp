@@ -5,7 +5,8 @@
 // (flame_hip_frontend_set_camera) flame_hip_frontend_track_raw puts the ingest stage (ingest.hip: grey, box downsample, undistort)
 // between the upload of the raw image and the tracker, writing into the ring slot the tracker reads.  flame_hip_frontend_debug_image
 // renders the Detections / Matches picture of the last tracked frame (frontend_debug.hip) from the record the tracker left on the
-// device.  Reads no environment variable.
+// device.  flame_hip_frontend_set_gates records the letterbox and the height band; every frame forms the gate record of FeFrame
+// from them and the frame's pose.  Reads no environment variable.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -66,6 +67,8 @@ struct flame_hip_frontend {
   uint8_t* d_dbg = nullptr;
   uint8_t* h_dbg = nullptr;
   double debug_image_device_us = 0.0;
+  // gates (set_gates): all zero = none
+  flame_hip_frontend_gates gates = {0, 0, 0.f, 0.f, {0.f, 0.f, 0.f}};
 };
 
 namespace {
@@ -135,6 +138,34 @@ int check_params(const flame_hip_frontend_params* p) {
       !(p->var_init > 0.f) || p->max_match_error < 0.f || p->max_match_error > 65025.f)
     return FLAME_HIP_ERR_ARG;
   return 0;
+}
+
+// the letterbox needs a band that holds a detection candidate's row with its window above and below
+int check_band(const flame_hip_frontend* fe, const flame_hip_frontend_params* p) {
+  if (!fe->gates.letterbox) return 0;
+  const int32_t y_lo = fe->H / 3, y_hi = fe->H - fe->H / 3;
+  return y_hi - y_lo < 2 * (p->win_size / 2 + 1) + 1 ? FLAME_HIP_ERR_ARG : 0;
+}
+
+// The frame's gate record: the band of rows, and hr = n^T R, h0 = n . t of T_world_cam = [R|t] in double (sums left to right),
+// each rounded once to float32 (tests/fe_gates_ref.py gate_record() is the same statement).
+FeGates gate_record(const flame_hip_frontend* fe, const double* T) {
+  FeGates g;
+  std::memset(&g, 0, sizeof(g));
+  const flame_hip_frontend_gates& s = fe->gates;
+  g.y_lo = s.letterbox ? fe->H / 3 : 0;
+  g.y_hi = s.letterbox ? fe->H - fe->H / 3 : fe->H;
+  g.height_gate = s.height_gate ? 1 : 0;
+  if (g.height_gate) {
+    const double n0 = s.up[0], n1 = s.up[1], n2 = s.up[2];
+    g.min_height = s.min_height;
+    g.max_height = s.max_height;
+    g.hr0 = (float)((n0 * T[0] + n1 * T[4]) + n2 * T[8]);
+    g.hr1 = (float)((n0 * T[1] + n1 * T[5]) + n2 * T[9]);
+    g.hr2 = (float)((n0 * T[2] + n1 * T[6]) + n2 * T[10]);
+    g.h0 = (float)((n0 * T[3] + n1 * T[7]) + n2 * T[11]);
+  }
+  return g;
 }
 
 // the raw image, rows made dense, into the page-locked staging buffer
@@ -268,18 +299,20 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
   f.epipolar_line_var = params->epipolar_line_var;
   f.bad_match_cost = (uint64_t)((double)params->max_match_error * (double)(f.win * f.win) * 65536.0);
   f.is_poseframe = is_poseframe ? 1 : 0;
+  f.gates = gate_record(fe, T_world_cam);
   const int32_t ncells = f.ncx * f.ncy;
   if (ncells > fe->cell_cap) {  // (grows with the smallest cell size seen; bounded by the image)
     FE_HIP(hipStreamSynchronize(fe->stream));
     if (fe->d_cell_key) (void)hipFree(fe->d_cell_key);
     if (fe->d_det) (void)hipFree(fe->d_det);
     fe->d_cell_key = nullptr; fe->d_det = nullptr; fe->cell_cap = 0;
-    FE_HIP(hipMalloc(&fe->d_cell_key, sizeof(unsigned long long) * (size_t)ncells));
+    FE_HIP(hipMalloc(&fe->d_cell_key, (sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)ncells));  // the keys, then the held flags
     FE_HIP(hipMalloc(&fe->d_det, sizeof(int32_t) * (size_t)ncells));
     fe->cell_cap = ncells;
     f.cell_key = fe->d_cell_key;
     f.det = fe->d_det;
   }
+  f.cell_held = reinterpret_cast<int32_t*>(fe->d_cell_key + ncells);  // (behind this frame's keys: one clear covers both)
   // a pose frame takes the ring's next slot; the features of the pose frame it overwrites die before tracking
   int32_t cur = fe->max_poseframes;  // the extra image slot
   bool overwrote = false;
@@ -305,7 +338,7 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
     FE_HIP(hipMemcpyAsync(fe->d_imgs + (size_t)cur * npix, fe->h_img, npix, hipMemcpyHostToDevice, s));
   }
   FE_HIP(hipMemcpyAsync(fe->d_poses, fe->h_poses, sizeof(FePose) * (size_t)fe->max_poseframes, hipMemcpyHostToDevice, s));
-  FE_HIP(hipMemsetAsync(fe->d_cell_key, 0xFF, sizeof(unsigned long long) * (size_t)ncells, s));
+  FE_HIP(hipMemsetAsync(fe->d_cell_key, 0xFF, (sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)ncells, s));
   FE_HIP(hipMemsetAsync(fe->d_counts, 0, sizeof(int32_t) * kFeCounts, s));
   if (overwrote) fe_launch_kill(s, f, valid_mask(fe));
   fe_launch_track(s, f);
@@ -348,6 +381,7 @@ int flame_hip_frontend_track(flame_hip_frontend* fe, const flame_hip_frontend_pa
   *n_out = 0;
   if (const int rc = check_params(params)) return rc;
   if (!finite12(T_world_cam)) return FLAME_HIP_ERR_NAN;
+  if (const int rc = check_band(fe, params)) return rc;
   if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
   return run_track(fe, params, img, pitch, false, img_id, T_world_cam, is_poseframe, n_out);
 }
@@ -388,6 +422,25 @@ int flame_hip_frontend_set_camera(flame_hip_frontend* fe, const flame_hip_camera
   return 0;
 }
 
+int flame_hip_frontend_set_gates(flame_hip_frontend* fe, const flame_hip_frontend_gates* gates) {
+  if (!fe) return FLAME_HIP_ERR_ARG;
+  flame_hip_frontend_gates g = {0, 0, 0.f, 0.f, {0.f, 0.f, 0.f}};
+  if (gates) {
+    g.letterbox = gates->letterbox ? 1 : 0;
+    if (gates->height_gate) {  // (the band and the up vector are read only with the gate on)
+      const float fl[] = {gates->min_height, gates->max_height, gates->up[0], gates->up[1], gates->up[2]};
+      for (float x : fl)
+        if (!std::isfinite(x)) return FLAME_HIP_ERR_NAN;
+      if (gates->min_height > gates->max_height || (gates->up[0] == 0.f && gates->up[1] == 0.f && gates->up[2] == 0.f)) return FLAME_HIP_ERR_ARG;
+      g.height_gate = 1;
+      g.min_height = gates->min_height; g.max_height = gates->max_height;
+      for (int k = 0; k < 3; ++k) g.up[k] = gates->up[k];
+    }
+  }
+  fe->gates = g;  // takes effect with the next frame
+  return 0;
+}
+
 int flame_hip_frontend_track_raw(flame_hip_frontend* fe, const flame_hip_frontend_params* params, const uint8_t* raw, int32_t pitch,
                                  uint32_t img_id, const double T_world_cam[12], int32_t is_poseframe, int32_t* n_out) {
   if (!fe || !params || !raw || !T_world_cam || !n_out) return FLAME_HIP_ERR_ARG;
@@ -396,6 +449,7 @@ int flame_hip_frontend_track_raw(flame_hip_frontend* fe, const flame_hip_fronten
   if (pitch < fe->cam.raw_w * in_channels(fe->cam.format)) return FLAME_HIP_ERR_ARG;
   if (const int rc = check_params(params)) return rc;
   if (!finite12(T_world_cam)) return FLAME_HIP_ERR_NAN;
+  if (const int rc = check_band(fe, params)) return rc;
   if (fe->device < 0) return FLAME_HIP_ERR_NODEVICE;
   return run_track(fe, params, raw, pitch, true, img_id, T_world_cam, is_poseframe, n_out);
 }
@@ -540,6 +594,9 @@ int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* va
   if (!std::strcmp(key, "ingest_device_us")) { *value = (int64_t)(fe->ingest_device_us + 0.5); return 0; }
   if (!std::strcmp(key, "ingest_raw_bytes")) { *value = fe->ingest_raw_bytes; return 0; }
   if (!std::strcmp(key, "debug_image_device_us")) { *value = (int64_t)(fe->debug_image_device_us + 0.5); return 0; }
+  if (!std::strcmp(key, "gates")) { *value = (fe->gates.letterbox ? 1 : 0) | (fe->gates.height_gate ? 2 : 0); return 0; }
+  if (!std::strcmp(key, "held_height")) { *value = fe->counts[10]; return 0; }
+  if (!std::strcmp(key, "refused_letterbox")) { *value = fe->counts[11]; return 0; }
   if (!std::strcmp(key, "camera")) { *value = fe->have_cam ? 1 : 0; return 0; }
   if (!std::strcmp(key, "poseframes")) {
     int64_t c = 0;

@@ -14,7 +14,8 @@ constexpr int kFeMaxWin = 9;
 
 // per-slot status of the last frame (FLAME_HIP_FE_* of include/flame_hip.h)
 enum { kFeOk = 0, kFeNoParallax = 1, kFeOutside = 2, kFeBadMatch = 3, kFeAmbiguous = 4, kFeNew = 5, kFeDied = 6, kFeFree = -1 };
-constexpr int kFeCounts = 16;  // counts[]: 0 = emitted, 1 = live, 2 + status = features of that status, 9 = detections dropped (no free slot)
+constexpr int kFeCounts = 16;  // counts[]: 0 = emitted, 1 = live, 2 + status = features of that status, 9 = detections dropped (no free slot),
+                               // 10 = features held by the height gate, 11 = projections refused by the letterbox
 
 // A = K R and c = K t of T_cur_ref, rounded once to float32 on the host (one record per pose-frame ring slot)
 struct FePose {
@@ -48,6 +49,15 @@ struct FeOut {
   int32_t slot, status;
 };
 
+// The gates of a frame (DESIGN.md 5.3 "Gates"), by value in FeFrame.  The letterbox band is the rows y_lo <= y < y_hi; without a
+// letterbox it is the whole image (y_lo = 0, y_hi = H), which leaves every test what it was.  The height of a projected feature is
+// ((hr0 bx + hr1 by) + hr2) / idepth + h0 with b = K^-1 (px, py, 1): hr = n^T R and h0 = n . t of T_world_cam, formed in double on
+// the host and rounded once to float32.
+struct FeGates {
+  int32_t y_lo, y_hi, height_gate;
+  float min_height, max_height, hr0, hr1, hr2, h0;
+};
+
 struct FeFrame {
   // geometry and parameters of this call
   int32_t W, H, max_features, win, dws, ncx, ncy, max_dropouts, g2_min, is_poseframe, cur_pf;
@@ -72,6 +82,7 @@ struct FeFrame {
   float4* proj;      // {x, y, idepth, var} in the current frame
   // per-frame grids and lists
   unsigned long long* cell_key;  // per cell: min over candidates of (bits(var_cur) << 32 | slot); all ones = empty
+  int32_t* cell_held;            // per cell, behind cell_key and cleared with it: all ones = no holder, 0 = a feature the height gate holds projects here
   int32_t* det;                  // per cell: y << 16 | x of the detection, -1 = none
   int32_t* freelist;             // max_features
   FeOut* out;                    // max_features
@@ -79,6 +90,7 @@ struct FeFrame {
   // the search record of the frame (debug images, flame_hip_frontend_searches): zero for a slot that ran no search
   float4* seg;     // {x0, y0, ex, ey}: sample k of the search sits at (x0 + k ex, y0 + k ey)
   int32_t* steps;  // S (0 = no search ran: free, NO_PARALLAX, OUTSIDE before the segment exists, NEW)
+  FeGates gates;
 };
 
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask);

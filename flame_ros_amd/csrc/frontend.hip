@@ -228,6 +228,9 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
     pok = px >= 0.0f && px <= (float)(f.W - 1) && py >= 0.0f && py <= (float)(f.H - 1) && fe_finite(xc) && fe_finite(vc) &&
           vc >= 0.0f;
   }
+  // the letterbox: a projection outside the band of rows fails like one outside the image (the band is the image without one)
+  const bool refused = pok && !(py >= (float)f.gates.y_lo && py <= (float)(f.gates.y_hi - 1));
+  pok = pok && !refused;
   if (failed || !pok) drop += 1;
   const bool dies = drop > f.max_dropouts;
   if (lane == 0) {
@@ -238,6 +241,7 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
     f.seg[slot] = seg;
     f.steps[slot] = steps;
     atomicAdd(&f.counts[2 + status], 1);
+    if (refused) atomicAdd(&f.counts[11], 1);
     if (dies) {
       f.alive[slot] = 0;
       f.status[slot] = kFeDied;
@@ -248,9 +252,22 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
       int cell = -1;
       if (pok) {
         cell = ((int)py / f.dws) * f.ncx + (int)px / f.dws;
-        // one emitted feature per cell: smallest variance, then lowest slot
-        atomicMin(&f.cell_key[cell], ((unsigned long long)__float_as_uint(vc) << 32) | (unsigned long long)(unsigned int)slot);
-        f.proj[slot] = make_float4(px, py, xc, vc);
+        bool held = false;
+        if (f.gates.height_gate) {  // height of the feature's world point along the caller's up vector (a NaN height is held)
+          const float bx = (px - f.cx) / f.fx, by = (py - f.cy) / f.fy;
+          const float height = ((f.gates.hr0 * bx + f.gates.hr1 * by) + f.gates.hr2) / xc + f.gates.h0;
+          held = !(height >= f.gates.min_height && height <= f.gates.max_height);
+        }
+        if (held) {
+          // not emitted and no candidate of its cell, but the cell stays occupied for the detection (every holder stores 0)
+          f.cell_held[cell] = 0;
+          atomicAdd(&f.counts[10], 1);
+          cell = -1;
+        } else {
+          // one emitted feature per cell: smallest variance, then lowest slot
+          atomicMin(&f.cell_key[cell], ((unsigned long long)__float_as_uint(vc) << 32) | (unsigned long long)(unsigned int)slot);
+          f.proj[slot] = make_float4(px, py, xc, vc);
+        }
       }
       f.cell_of[slot] = cell;
     }
@@ -262,13 +279,14 @@ __global__ __launch_bounds__(256) void k_fe_detect(FeFrame f) {
   const int lane = threadIdx.x & 63;
   const int cell = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (cell >= f.ncx * f.ncy) return;
-  if (f.cell_key[cell] != kNone) {  // occupied by an emitted feature of this frame
+  // occupied by an emitted feature of this frame, or by one the height gate holds
+  if (f.cell_key[cell] != kNone || (f.gates.height_gate && f.cell_held[cell] == 0)) {
     if (lane == 0) f.det[cell] = -1;
     return;
   }
   const int ccx = cell % f.ncx, ccy = cell / f.ncx, m = (f.win >> 1) + 1;
   const int xlo = max(ccx * f.dws, m), xhi = min(ccx * f.dws + f.dws, f.W - m);
-  const int ylo = max(ccy * f.dws, m), yhi = min(ccy * f.dws + f.dws, f.H - m);
+  const int ylo = max(max(ccy * f.dws, m), f.gates.y_lo), yhi = min(min(ccy * f.dws + f.dws, f.H - m), f.gates.y_hi);
   const int cw = xhi - xlo, ch = yhi - ylo;
   unsigned long long best = 0ull;
   if (cw > 0 && ch > 0) {

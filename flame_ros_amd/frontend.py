@@ -31,6 +31,12 @@ class Camera(C.Structure):
                 ("D", C.c_float * 5)]
 
 
+class Gates(C.Structure):
+    """flame_hip_frontend_gates."""
+    _fields_ = [("letterbox", C.c_int32), ("height_gate", C.c_int32), ("min_height", C.c_float), ("max_height", C.c_float),
+                ("up", C.c_float * 3)]
+
+
 def default_frontend_params(**overrides):
     """The library's defaults (flame::Params' feature fields + the front end's own), with overrides."""
     p = FrontEndParams()
@@ -104,6 +110,19 @@ class GpuFrontEnd:
         cam = Camera(int(raw_width), int(raw_height), int(format), int(resize_factor), (C.c_float * 5)(*[float(d) for d in D]))
         _l.check(self._lib.flame_hip_frontend_set_camera(self._h, C.byref(cam)), "flame_hip_frontend_set_camera")
         self._cam = cam
+
+    def set_gates(self, letterbox=False, min_height=None, max_height=None, up=(0, -1, 0)):
+        """The gates of the frames to come: `letterbox` keeps features in the middle third of the rows; a `min_height` and / or
+        `max_height` holds back every tracked feature whose world point lies outside that band along `up` (not normalised;
+        (0, -1, 0) for a right-down-forward world).  `set_gates()`: none."""
+        height = min_height is not None or max_height is not None
+        if not letterbox and not height:
+            _l.check(self._lib.flame_hip_frontend_set_gates(self._h, None), "flame_hip_frontend_set_gates")
+            return
+        big = float(np.finfo(np.float32).max)
+        g = Gates(int(bool(letterbox)), int(height), -big if min_height is None else float(min_height),
+                  big if max_height is None else float(max_height), (C.c_float * 3)(*[float(a) for a in up]))
+        _l.check(self._lib.flame_hip_frontend_set_gates(self._h, C.byref(g)), "flame_hip_frontend_set_gates")
 
     def _raw(self, raw):
         cam = getattr(self, "_cam", None)

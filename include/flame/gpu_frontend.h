@@ -19,6 +19,14 @@
 // front of the tracker: update() then takes the grey image as the camera delivers it, raw_width x raw_height, and the K both
 // objects were made with is the K of the rectified image (K_raw / resize_factor).  frontEnd() binds `rectified` as well, so the
 // stages of Flame that read pixels (the evaluate stage) get the rectified image, downloaded once per frame and only when asked.
+//
+// GATES (flame_hip.h, flame_hip_frontend_set_gates; DESIGN.md 5.3 "Gates"): the constructor honours Params::do_letterbox
+// (features only in the middle third of the rows) and Params::min_height / max_height (a tracked feature whose world point lies
+// outside that band along the up axis is held back from the mesh); the height band is on iff min_height > -1e14f or max_height <
+// 1e14f, so the reference's defaults set no gate and nothing changes.  setUpAxis() names the world's up direction (default
+// (0, -1, 0): the reference's camera_world frame is right-down-forward [UPSTREAM-RECALL]); setGates() changes the gates later.  A
+// record the library refuses (min_height > max_height, a zero or non-finite up axis, ...) leaves its code in lastError() and
+// fails every track() until a valid one is set -- the gates are never dropped silently.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -47,6 +55,12 @@ class GpuFrontEnd {
     fparams_.max_dropouts = params.max_dropouts;
     last_error_ = flame_hip_frontend_create(&handle_, params.hip_device, width, height, Kr, max_features, max_poseframes);
     if (last_error_) handle_ = nullptr;
+    gates_.letterbox = params.do_letterbox ? 1 : 0;
+    gates_.height_gate = (params.min_height > -1e14f || params.max_height < 1e14f) ? 1 : 0;
+    gates_.min_height = params.min_height;
+    gates_.max_height = params.max_height;
+    gates_.up[0] = 0.f; gates_.up[1] = -1.f; gates_.up[2] = 0.f;
+    if (handle_ && (gates_.letterbox || gates_.height_gate)) applyGates();  // (the reference's defaults: no call at all)
   }
   ~GpuFrontEnd() { flame_hip_frontend_destroy(handle_); }
   GpuFrontEnd(const GpuFrontEnd&) = delete;
@@ -82,6 +96,22 @@ class GpuFrontEnd {
     return have_camera_;
   }
   bool hasCamera() const { return have_camera_; }
+
+  // The gates of the frames to come.  setGates: the letterbox switch and the height band (height_gate = false: no band, the two
+  // heights are not read); setUpAxis: the world direction heights are measured along (not normalised).  false (lastError()) when
+  // the library refuses the record; track() then fails until a valid one is set.
+  bool setGates(bool letterbox, bool height_gate, float min_height = -1e14f, float max_height = 1e14f) {
+    gates_.letterbox = letterbox ? 1 : 0;
+    gates_.height_gate = height_gate ? 1 : 0;
+    gates_.min_height = min_height;
+    gates_.max_height = max_height;
+    return applyGates();
+  }
+  bool setUpAxis(float x, float y, float z) {
+    gates_.up[0] = x; gates_.up[1] = y; gates_.up[2] = z;
+    return applyGates();
+  }
+  const flame_hip_frontend_gates& gates() const { return gates_; }
 
   // The ingest stage alone (flame_hip_frontend_rectify): `out` becomes the width x height rectified image of `raw`; the
   // feature state is untouched.
@@ -124,6 +154,7 @@ class GpuFrontEnd {
 
   bool track(const FrameInput& in, FeatureSet* out) {
     if (!handle_) return false;  // (lastError() still holds why the handle could not be made)
+    if (gates_error_) return fail(gates_error_);  // (a refused gate record is not tracked around)
     rectified_valid_ = false;
     const int rows = have_camera_ ? raw_height_ : height_, cols = have_camera_ ? raw_width_ : width_;
     if (!in.img || !out || in.img->rows != rows || in.img->cols != cols) return fail(FLAME_HIP_ERR_ARG);
@@ -170,6 +201,12 @@ class GpuFrontEnd {
       int64_t v = 0;
       if (flame_hip_frontend_info(handle_, kKeys[k][1], &v) == 0) stats->set(kKeys[k][0], static_cast<double>(v));
     }
+    // this build's own keys, with a gate on only: features the height band held, projections the letterbox refused
+    int64_t g = 0, v = 0;
+    if (flame_hip_frontend_info(handle_, "gates", &g) == 0 && g != 0) {
+      if (flame_hip_frontend_info(handle_, "held_height", &v) == 0) stats->set("num_held_height", static_cast<double>(v));
+      if (flame_hip_frontend_info(handle_, "refused_letterbox", &v) == 0) stats->set("num_refused_letterbox", static_cast<double>(v));
+    }
   }
 
   // [R|t], row-major 3x4 in double (flame/types.h poseToRt, shared with Flame's prediction stage)
@@ -180,6 +217,12 @@ class GpuFrontEnd {
     last_error_ = code;
     return false;
   }
+  bool applyGates() {
+    if (!handle_) return false;
+    gates_error_ = flame_hip_frontend_set_gates(handle_, (gates_.letterbox || gates_.height_gate) ? &gates_ : nullptr);
+    last_error_ = gates_error_;
+    return gates_error_ == 0;
+  }
   static int32_t pitchOf(const Image1b& img) {
     return img.rows > 1 ? static_cast<int32_t>(img.ptr<uint8_t>(1) - img.ptr<uint8_t>(0)) : img.cols;
   }
@@ -189,6 +232,8 @@ class GpuFrontEnd {
   Image1b rectified_;             // the image of the last track(), downloaded on demand
   bool rectified_valid_ = false;
   flame_hip_frontend_params fparams_;
+  flame_hip_frontend_gates gates_;
+  int gates_error_ = 0;  // what the library said to the last gate record
   flame_hip_frontend* handle_ = nullptr;
   int last_error_ = 0;
 };

@@ -71,6 +71,7 @@ struct Params {
   // nor pose).  Off by default: with it off update() makes exactly the calls it made before and none of the keys appears.
   bool photo_error = false;
   // features (:209-231)
+  // do_letterbox ("Process only middle third of image"): honoured by flame::GpuFrontEnd (gpu_frontend.h; DESIGN.md 5.3 "Gates")
   bool do_letterbox = false;
   float min_grad_mag = 5.0f;
   float min_error = 100.0f;
@@ -92,8 +93,11 @@ struct Params {
   optimizers::nltgv2_l1_graph_regularizer::Params rparams;
   // min_height / max_height ("height of features that are added to graph", yaml :97-98) and
   // check_sticky_obstacles (:99) gate FEATURES, upstream of the variance gate, in the feature
-  // pipeline that is not rebuilt here: carried for the frontends and a registered FrontEnd,
-  // IGNORED by the GPU tail (the reference defaults +-1e14 / false disable them anyway).
+  // pipeline.  min_height / max_height are honoured by flame::GpuFrontEnd (gpu_frontend.h: the band
+  // is on iff min_height > -1e14f or max_height < 1e14f, heights along GpuFrontEnd::setUpAxis;
+  // DESIGN.md 5.3 "Gates"); for any other registered FrontEnd they are only carried, and the GPU
+  // tail behind the features never reads them.  check_sticky_obstacles is carried and honoured by
+  // nobody: the reference does not say what it does.
   float min_height = -1e14f, max_height = 1e14f;
   bool check_sticky_obstacles = false;
   // [UPSTREAM-RECALL] switches (not in the reference; defaults = the build's statement, see

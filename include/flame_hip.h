@@ -548,7 +548,8 @@ int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* 
  * its device work); features of the last frame per status: "ok", "no_parallax", "outside", "bad_match", "ambiguous", "new",
  * "died"; "detections_dropped" (no free slot), "max_features"; "camera" (1 = a camera is set), "ingest_device_us" (HIP events
  * around the raw upload and the ingest stage of the last _track_raw / _rectify; 0 after a _track), "ingest_raw_bytes" (what that
- * call uploaded) */
+ * call uploaded); "gates" (bit 0 = letterbox, bit 1 = height band: what _set_gates last set), "held_height" / "refused_letterbox"
+ * (features of the last frame the height band held / whose projection the letterbox refused) */
 int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value);
 /* Debug/test hook: every slot's state (max_features entries each; any pointer may be NULL): alive, reference pixel (u, v),
  * ring slot of its pose frame, prior (mu, var) in the pose frame, dropout counter, last status (-1 = free), last best sample. */
@@ -613,6 +614,28 @@ int flame_hip_frontend_track_raw(flame_hip_frontend* fe, const flame_hip_fronten
 int flame_hip_frontend_rectify(flame_hip_frontend* fe, const uint8_t* raw, int32_t pitch, uint8_t* out, int32_t out_pitch);
 /* The image the last _track / _track_raw call tracked (after the ingest stage), downloaded; STATE before the first frame. */
 int flame_hip_frontend_image(flame_hip_frontend* fe, uint8_t* out, int32_t out_pitch);
+
+/* ---- gates (opt-in): the reference's features/do_letterbox ("Process only middle third of image") and
+ * regularization/nltgv2/{min_height, max_height} ("Minimum / maximum height of features that are added to graph"), evaluated in
+ * the tracker and the detector (DESIGN.md 5.3 "Gates"; restated in tests/fe_gates_ref.py, which the GPU equals bit for bit).
+ *   letterbox: y_lo = H / 3, y_hi = H - H / 3 (integer division).  A tracked feature whose projection has py < y_lo or py > y_hi - 1
+ *     (compared in float) fails its projection exactly like one outside the image: not emitted, one dropout.  Detection candidates
+ *     are restricted to the rows y_lo <= y < y_hi.  Searches and reference windows still read the whole image.
+ *   height_gate: height = ((hr0 bx + hr1 by) + hr2) / idepth + h0 of a projected feature, b = K^-1 (px, py, 1), hr = up^T R and
+ *     h0 = up . t of the frame's T_world_cam = [R|t] (formed in double, rounded once to float32).  Unless min_height <= height <=
+ *     max_height (a NaN height fails) the feature is HELD: tracked and fused as usual, not emitted, no candidate of its cell -- a
+ *     feature of larger variance in the band is emitted instead -- but its cell gets no detection.  A NEW feature is emitted ungated.
+ *   up is not normalised by the library; (0, -1, 0) suits a right-down-forward world frame.
+ * NULL, or both switches 0: no gate, every call does what it did before.  Takes effect with the next frame.  Valid on a handle
+ * without a device.  Errors: NAN (non-finite min_height, max_height or up with height_gate != 0), ARG (NULL fe; with height_gate
+ * != 0: min_height > max_height, up all zero).  A letterbox band narrower than 2 (win_size / 2 + 1) + 1 rows makes the next
+ * _track / _track_raw return ARG (before any device work). */
+typedef struct {
+  int32_t letterbox, height_gate;
+  float min_height, max_height;
+  float up[3];
+} flame_hip_frontend_gates;
+int flame_hip_frontend_set_gates(flame_hip_frontend* fe, const flame_hip_frontend_gates* gates /* NULL = none */);
 
 /* Debug/test hook (no device needed; works on a handle created with device = -1): copies the
  * named host-side plan array ("v_o2i", "e_o2i", "grow", "ginc", "eij", "tiles", "t_vmap",

@@ -32,6 +32,11 @@
 // gets setCamera and takes the raw image: no separate rectify call, no host undistortion.  Not together with --dump.
 // --debug-images dir (needs --gpu-frontend): Params::debug_draw_detections / debug_draw_matches on; after every frame
 // dir/detections_<id>.ppm and dir/matches_<id>.ppm (binary P6, RGB) from getDebugImageDetections() / getDebugImageMatches().
+// --letterbox, --min-height H, --max-height H, --up-axis x,y,z (need --gpu-frontend): the reference's features/do_letterbox and
+// regularization/nltgv2/{min_height, max_height} (Params::do_letterbox / min_height / max_height, honoured by flame::GpuFrontEnd:
+// features only in the middle third of the rows; tracked features whose world point lies outside the height band along the up
+// axis -- default 0,-1,0 -- are held back from the mesh).  With one of them the frame line ends with `held_height <n>
+// refused_letterbox <n>`; a band the library refuses ends the run with exit code 5.
 // --dump dir: frame_<id>.bin = {int32 V, T; float pos[2V], idepth_mu[V], idepth_var[V]; int32 tris[3T]; float idepth[V]}:
 // what went into the regulariser and what came out, for a bit-for-bit comparison with the oracle (tests).
 #include <cmath>
@@ -68,6 +73,10 @@ struct Lite {
   std::unique_ptr<flame::GpuFrontEnd> gpu;  // --gpu-frontend: the feature pipeline
   bool raw_camera = false;                  // ... which takes raw images and rectifies them itself (asl --gpu-rectify)
   float D[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  bool gates = false;  // --letterbox / --min-height / --max-height given
+  bool have_up = false;
+  float up[3] = {0.f, -1.f, 0.f};
+  int gates_error = 0;
 
   flame::FrontEnd frontEnd() {
     flame::FrontEnd fe;
@@ -98,6 +107,11 @@ struct Lite {
     if (gpu_frontend) {
       gpu.reset(new flame::GpuFrontEnd(W, H, K, params));
       if (raw_camera && !gpu->setCamera(W, H, 1, D)) std::fprintf(stderr, "--gpu-rectify: hip_error %d\n", gpu->lastError());
+      if (gates && gpu->handle()) {  // (Params carried the band into the constructor; the up axis is the front end's own)
+        gates_error = gpu->gates().letterbox || gpu->gates().height_gate ? gpu->lastError() : 0;
+        if (!gates_error && have_up && !gpu->setUpAxis(up[0], up[1], up[2])) gates_error = gpu->lastError();
+        if (gates_error) std::fprintf(stderr, "gates: hip_error %d\n", gates_error);
+      }
       sensor->setFrontEnd(gpu->frontEnd());
     } else {
       sensor->setFrontEnd(frontEnd());
@@ -173,6 +187,14 @@ struct Lite {
     if (params.photo_error)  // (appended at the end: without the flag the line is what it was)
       std::printf(" photo_total %.6f photo_avg %.6f photo_pixels %d", st.stats("total_photo_error"), st.stats("avg_photo_error"),
                   static_cast<int>(st.stats("photo_pixels")));
+    if (gates) {  // (appended at the end: without the flags the line is what it was)
+      int64_t held = 0, refused = 0;
+      if (gpu && gpu->handle()) {
+        flame_hip_frontend_info(gpu->handle(), "held_height", &held);
+        flame_hip_frontend_info(gpu->handle(), "refused_letterbox", &refused);
+      }
+      std::printf(" held_height %d refused_letterbox %d", static_cast<int>(held), static_cast<int>(refused));
+    }
     std::printf("\n");
   }
 };
@@ -182,7 +204,7 @@ struct Lite {
 int main(int argc, char** argv) {
   std::vector<char*> args;
   Lite L;
-  bool gpu_rectify = false;
+  bool gpu_rectify = false, bad_up = false;
   for (int k = 1; k < argc; ++k) {
     if (!std::strcmp(argv[k], "--dump") && k + 1 < argc) L.dump_dir = argv[++k];
     else if (!std::strcmp(argv[k], "--project-graph")) L.params.project_graph = true;  // warm-start every frame from the last mesh
@@ -190,14 +212,23 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[k], "--gpu-rectify")) gpu_rectify = true;               // (asl) undistort on the GPU
     else if (!std::strcmp(argv[k], "--gpu-frontend")) L.gpu_frontend = true;           // features from flame::GpuFrontEnd
     else if (!std::strcmp(argv[k], "--debug-images") && k + 1 < argc) L.debug_dir = argv[++k];
+    else if (!std::strcmp(argv[k], "--letterbox")) { L.params.do_letterbox = true; L.gates = true; }
+    else if (!std::strcmp(argv[k], "--min-height") && k + 1 < argc) { L.params.min_height = static_cast<float>(std::atof(argv[++k])); L.gates = true; }
+    else if (!std::strcmp(argv[k], "--max-height") && k + 1 < argc) { L.params.max_height = static_cast<float>(std::atof(argv[++k])); L.gates = true; }
+    else if (!std::strcmp(argv[k], "--up-axis") && k + 1 < argc) {
+      L.have_up = std::sscanf(argv[++k], "%f,%f,%f", &L.up[0], &L.up[1], &L.up[2]) == 3;
+      if (!L.have_up) bad_up = true;
+    }
     else args.push_back(argv[k]);
   }
   const bool asl = !args.empty() && !std::strcmp(args[0], "asl");
   if (!args.empty() && (!std::strcmp(args[0], "tum") || asl)) args.erase(args.begin());
-  const bool bad_flags = (!L.debug_dir.empty() && !L.gpu_frontend) || (!L.dump_dir.empty() && L.gpu_frontend);
+  const bool bad_flags = (!L.debug_dir.empty() && !L.gpu_frontend) || (!L.dump_dir.empty() && L.gpu_frontend) ||
+                         ((L.gates || L.have_up) && !L.gpu_frontend) || bad_up;
   if (bad_flags || (asl && args.size() < 4) || (!asl && args.size() < 6)) {
     std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-frontend [--debug-images dir]]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-rectify] [--gpu-frontend [--debug-images dir]]\n"
-                 "  --gpu-frontend: features from the GPU tracker (not with --dump); --debug-images dir: detections_<id>.ppm / matches_<id>.ppm per frame (needs --gpu-frontend)\n",
+                 "  --gpu-frontend: features from the GPU tracker (not with --dump); --debug-images dir: detections_<id>.ppm / matches_<id>.ppm per frame (needs --gpu-frontend)\n"
+                 "  --letterbox, --min-height H, --max-height H, --up-axis x,y,z (need --gpu-frontend): features only in the middle third of the rows / only inside the height band along the up axis (default 0,-1,0)\n",
                  argv[0], argv[0]);
     return 2;
   }
@@ -246,6 +277,7 @@ int main(int argc, char** argv) {
         for (int y = 0; y < L.H; ++y) std::memcpy(gray.data() + static_cast<size_t>(y) * L.W, rect.ptr<uint8_t>(y), L.W);
       }
       if (!L.sensor) L.construct(cam.fx, cam.fy, cam.cx, cam.cy);
+      if (L.gates_error) return 5;
       L.frame(id, fr.time, fr.pose_optical, gray);
     }
   } else {
@@ -264,6 +296,7 @@ int main(int argc, char** argv) {
         return 4;
       }
       if (!L.sensor) L.construct(fx, fy, cx, cy);
+      if (L.gates_error) return 5;
       L.frame(id, fr.time, fr.pose_optical, gray);
     }
   }

@@ -8,7 +8,11 @@ cells + slot assignment + compaction; the tracking frame = upload + 1 200 search
 most priors are narrower.  Times: HIP events around the call's device work (image upload to counts download) and the host's
 wall time of the whole call, median over the pairs after a warm-up.
 
-    python tools/frontend_bench.py [--frames 100] [--warmup 10]
+--gates: the same pairs with both gates on (GpuFrontEnd.set_gates: the letterbox and a height band of +-0.15 about the camera
+along the default up axis, which holds about half of the features the letterbox leaves; only a third of the cells detect, so
+fewer features live) -- what the compares, the height and the held-cell flag cost where they act.
+
+    python tools/frontend_bench.py [--frames 100] [--warmup 10] [--gates]
 """
 import argparse
 import json
@@ -33,7 +37,7 @@ def texture(h, w, seed=5, factor=8):
     return np.floor(up + 0.5).astype(np.uint8)
 
 
-def run(frames=100, warmup=10, W=640, H=480, shift=6):
+def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False):
     from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
     K = np.array([525, 0, 319.5, 0, 525, 239.5, 0, 0, 1], np.float32)
     big = texture(H, W + shift)
@@ -44,7 +48,9 @@ def run(frames=100, warmup=10, W=640, H=480, shift=6):
     p = default_frontend_params()
     t = {"poseframe": {"device": [], "host": []}, "tracking": {"device": [], "host": []}}
     with GpuFrontEnd(W, H, K, max_features=2048, max_poseframes=1) as fe:
-        live = ok = 0
+        live = ok = held = refused = 0
+        if gates:
+            fe.set_gates(letterbox=True, min_height=-0.15, max_height=0.15)
         for i in range(warmup + frames):
             for kind, img, T, pf in (("poseframe", a, Ta, True), ("tracking", b, Tb, False)):
                 fe.track(p, img, 2 * i + (not pf), T, pf)
@@ -52,7 +58,11 @@ def run(frames=100, warmup=10, W=640, H=480, shift=6):
                     t[kind]["device"].append(fe.info("track_device_us"))
                     t[kind]["host"].append(fe.info("track_us"))
             live, ok = fe.info("live"), fe.info("ok")
+            if gates:
+                held, refused = fe.info("held_height"), fe.info("refused_letterbox")
     res = {"width": W, "height": H, "live_features": live, "matched_ok": ok, "pairs": frames}
+    if gates:
+        res.update(gates=3, held_height=held, refused_letterbox=refused)
     for kind in t:
         res[kind + "_device_us"] = float(np.median(t[kind]["device"]))
         res[kind + "_host_us"] = float(np.median(t[kind]["host"]))
@@ -63,5 +73,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--gates", action="store_true")
     a = ap.parse_args()
-    print(json.dumps({"frontend_track": run(max(a.frames, 50), a.warmup)}))
+    print(json.dumps({"frontend_track": run(max(a.frames, 50), a.warmup, gates=a.gates)}))
