@@ -6,7 +6,8 @@
 // between the upload of the raw image and the tracker, writing into the ring slot the tracker reads.  flame_hip_frontend_debug_image
 // renders the Detections / Matches picture of the last tracked frame (frontend_debug.hip) from the record the tracker left on the
 // device.  flame_hip_frontend_set_gates records the letterbox and the height band; every frame forms the gate record of FeFrame
-// from them and the frame's pose.  Reads no environment variable.
+// from them and the frame's pose.  flame_hip_frontend_set_cost records the matching cost (SSD / ZSSD); every frame forms the BAD_MATCH
+// threshold of that cost and picks the tracker's instantiation.  Reads no environment variable.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -69,6 +70,8 @@ struct flame_hip_frontend {
   double debug_image_device_us = 0.0;
   // gates (set_gates): all zero = none
   flame_hip_frontend_gates gates = {0, 0, 0.f, 0.f, {0.f, 0.f, 0.f}};
+  // matching cost (set_cost): no state depends on it, so it may change between any two frames
+  int32_t cost_mode = FLAME_HIP_FE_COST_SSD;
 };
 
 namespace {
@@ -166,6 +169,15 @@ FeGates gate_record(const flame_hip_frontend* fe, const double* T) {
     g.h0 = (float)((n0 * T[3] + n1 * T[7]) + n2 * T[11]);
   }
   return g;
+}
+
+// The BAD_MATCH threshold of a frame (DESIGN.md 5.3 "Matching cost"): bad = max_match_error win^2 65536 bounds the SSD cost; the
+// ZSSD cost n S2 - S1^2 is bounded by n bad, saturated at UINT64_MAX (tests/fe_zm_ref.py bad_threshold() is the same statement).
+uint64_t bad_threshold(float max_match_error, int32_t win, int32_t cost_mode) {
+  const uint64_t n = (uint64_t)(win * win);
+  const uint64_t bad = (uint64_t)((double)max_match_error * (double)(win * win) * 65536.0);
+  if (cost_mode != FLAME_HIP_FE_COST_ZSSD) return bad;
+  return bad > UINT64_MAX / n ? UINT64_MAX : n * bad;
 }
 
 // the raw image, rows made dense, into the page-locked staging buffer
@@ -297,7 +309,8 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
   f.idepth_min = params->idepth_min; f.idepth_max = params->idepth_max;
   f.idepth_init = params->idepth_init; f.var_init = params->var_init;
   f.epipolar_line_var = params->epipolar_line_var;
-  f.bad_match_cost = (uint64_t)((double)params->max_match_error * (double)(f.win * f.win) * 65536.0);
+  const bool zero_mean = fe->cost_mode == FLAME_HIP_FE_COST_ZSSD;
+  f.bad_match_cost = bad_threshold(params->max_match_error, f.win, fe->cost_mode);
   f.is_poseframe = is_poseframe ? 1 : 0;
   f.gates = gate_record(fe, T_world_cam);
   const int32_t ncells = f.ncx * f.ncy;
@@ -341,7 +354,7 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
   FE_HIP(hipMemsetAsync(fe->d_cell_key, 0xFF, (sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)ncells, s));
   FE_HIP(hipMemsetAsync(fe->d_counts, 0, sizeof(int32_t) * kFeCounts, s));
   if (overwrote) fe_launch_kill(s, f, valid_mask(fe));
-  fe_launch_track(s, f);
+  fe_launch_track(s, f, zero_mean);
   if (is_poseframe) fe_launch_detect(s, f);
   fe_launch_compact(s, f);
   FE_HIP(hipGetLastError());
@@ -438,6 +451,12 @@ int flame_hip_frontend_set_gates(flame_hip_frontend* fe, const flame_hip_fronten
     }
   }
   fe->gates = g;  // takes effect with the next frame
+  return 0;
+}
+
+int flame_hip_frontend_set_cost(flame_hip_frontend* fe, int32_t mode) {
+  if (!fe || (mode != FLAME_HIP_FE_COST_SSD && mode != FLAME_HIP_FE_COST_ZSSD)) return FLAME_HIP_ERR_ARG;
+  fe->cost_mode = mode;  // takes effect with the next frame
   return 0;
 }
 
@@ -595,6 +614,7 @@ int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* va
   if (!std::strcmp(key, "ingest_raw_bytes")) { *value = fe->ingest_raw_bytes; return 0; }
   if (!std::strcmp(key, "debug_image_device_us")) { *value = (int64_t)(fe->debug_image_device_us + 0.5); return 0; }
   if (!std::strcmp(key, "gates")) { *value = (fe->gates.letterbox ? 1 : 0) | (fe->gates.height_gate ? 2 : 0); return 0; }
+  if (!std::strcmp(key, "cost_mode")) { *value = fe->cost_mode; return 0; }
   if (!std::strcmp(key, "held_height")) { *value = fe->counts[10]; return 0; }
   if (!std::strcmp(key, "refused_letterbox")) { *value = fe->counts[11]; return 0; }
   if (!std::strcmp(key, "camera")) { *value = fe->have_cam ? 1 : 0; return 0; }

@@ -94,7 +94,7 @@ struct FeFrame {
 };
 
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask);
-void fe_launch_track(hipStream_t s, const FeFrame& f);
+void fe_launch_track(hipStream_t s, const FeFrame& f, bool zero_mean);  // zero_mean: the ZSSD cost (f.bad_match_cost is that cost's threshold)
 void fe_launch_detect(hipStream_t s, const FeFrame& f);
 void fe_launch_compact(hipStream_t s, const FeFrame& f);
 

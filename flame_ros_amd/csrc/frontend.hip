@@ -39,6 +39,10 @@ __device__ __forceinline__ bool fe_finite(float x) { return __builtin_fabsf(x) <
 // Cost of one sample: sum over the win x win window of (bilinear(cur, p) * 256 - 256 * ref)^2 with p quantised to 1/16 px;
 // kNone when the window (with its +1 bilinear neighbours) leaves the image.  Per row two running pixels are carried, so a
 // window pixel costs two loads of the current image and one of the reference patch.
+// ZM (DESIGN.md 5.3 "Matching cost", mode ZSSD): with D_i the n = win^2 differences, S1 = sum D_i (|S1| <= 81 * 65 280: an int32)
+// and S2 = sum D_i^2, the cost is n S2 - S1^2 -- n^2 times the variance of D over the window, >= 0, <= (n^2 - 1) 65 280^2 < 2^45,
+// and the same integer whatever constant a frame's exposure adds to every D_i.
+template <bool ZM>
 __device__ __forceinline__ unsigned long long fe_cost(const FeFrame& f, const uint8_t* __restrict__ ref, int u, int v, float px,
                                                       float py) {
   const float fqx = floorf(px * 16.0f + 0.5f), fqy = floorf(py * 16.0f + 0.5f);
@@ -49,6 +53,7 @@ __device__ __forceinline__ unsigned long long fe_cost(const FeFrame& f, const ui
   if (ix - r < 0 || iy - r < 0 || ix + r + 1 > f.W - 1 || iy + r + 1 > f.H - 1) return kNone;
   const int wx1 = qx & 15, wx0 = 16 - wx1, wy1 = qy & 15, wy0 = 16 - wy1;
   unsigned long long C = 0;
+  int S1 = 0;
   for (int dy = -r; dy <= r; ++dy) {
     const uint8_t* __restrict__ r0 = f.cur + (size_t)(iy + dy) * f.W + (ix - r);
     const uint8_t* __restrict__ r1 = r0 + f.W;
@@ -59,9 +64,14 @@ __device__ __forceinline__ unsigned long long fe_cost(const FeFrame& f, const ui
       const int D = wy0 * (wx0 * t0 + wx1 * t1) + wy1 * (wx0 * b0 + wx1 * b1) - 256 * (int)rr[dx];
       const unsigned int aD = (unsigned int)(D < 0 ? -D : D);  // <= 65 280: the square fits 32 bits
       C += (unsigned long long)(aD * aD);
+      if (ZM) S1 += D;
       t0 = t1;
       b0 = b1;
     }
+  }
+  if (ZM) {
+    const unsigned int a1 = (unsigned int)(S1 < 0 ? -S1 : S1);
+    C = (unsigned long long)(unsigned int)(f.win * f.win) * C - (unsigned long long)a1 * (unsigned long long)a1;
   }
   return C;
 }
@@ -72,6 +82,9 @@ __global__ __launch_bounds__(256) void k_fe_kill(FeFrame f, unsigned long long v
   if (f.alive[slot] && !((valid_mask >> f.pf[slot]) & 1ull)) f.alive[slot] = 0;
 }
 
+// ZM picks the matching cost (false: SSD, true: ZSSD); f.bad_match_cost is the host's threshold for that cost.  Everything
+// behind the cost -- argmin, BAD_MATCH, AMBIGUOUS, the parabola -- takes it as it comes.
+template <bool ZM>
 __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
   const int lane = threadIdx.x & 63;
   const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -129,9 +142,9 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
       for (int pass = 0; pass < kFePasses; ++pass) {
         const int k = lane + 64 * pass;
         unsigned long long c = kNone;
-        if (64 * pass <= S && k <= S) c = fe_cost(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey);
+        if (64 * pass <= S && k <= S) c = fe_cost<ZM>(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey);
         C[pass] = c;
-        if (c != kNone) {  // (c < 2^39, k < 2^9: one 64-bit key orders by cost, then by k)
+        if (c != kNone) {  // (c < 2^39 -- ZM: c < 2^45 --, k < 2^9: one 64-bit key < 2^54 orders by cost, then by k)
           const unsigned long long key = (c << 9) | (unsigned long long)k;
           best = key < best ? key : best;
         }
@@ -402,8 +415,9 @@ __global__ __launch_bounds__(1024) void k_fe_compact(FeFrame f) {
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask) {
   hipLaunchKernelGGL(k_fe_kill, dim3((f.max_features + 255) / 256), dim3(256), 0, s, f, valid_mask);
 }
-void fe_launch_track(hipStream_t s, const FeFrame& f) {
-  hipLaunchKernelGGL(k_fe_track, dim3((f.max_features + 3) / 4), dim3(256), 0, s, f);
+void fe_launch_track(hipStream_t s, const FeFrame& f, bool zero_mean) {
+  if (zero_mean) hipLaunchKernelGGL(k_fe_track<true>, dim3((f.max_features + 3) / 4), dim3(256), 0, s, f);
+  else hipLaunchKernelGGL(k_fe_track<false>, dim3((f.max_features + 3) / 4), dim3(256), 0, s, f);
 }
 void fe_launch_detect(hipStream_t s, const FeFrame& f) {
   hipLaunchKernelGGL(k_fe_detect, dim3((f.ncx * f.ncy + 3) / 4), dim3(256), 0, s, f);

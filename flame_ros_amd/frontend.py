@@ -12,6 +12,7 @@ from . import lib as _l
 from .lib import FlameHipError  # noqa: F401
 
 FE_OK, FE_NO_PARALLAX, FE_OUTSIDE, FE_BAD_MATCH, FE_AMBIGUOUS, FE_NEW, FE_DIED, FE_FREE = 0, 1, 2, 3, 4, 5, 6, -1
+COST_SSD, COST_ZSSD = 0, 1  # FLAME_HIP_FE_COST_*: the matching cost (set_cost)
 STATUS_KEYS = ("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died")
 IMG_DETECTIONS, IMG_MATCHES = _l.FE_IMG_DETECTIONS, _l.FE_IMG_MATCHES  # FLAME_HIP_FE_IMG_*
 PIX_CHANNELS = {_l.PIX_GRAY8: 1, _l.PIX_BGR8: 3, _l.PIX_RGB8: 3, _l.PIX_BGRA8: 4, _l.PIX_RGBA8: 4}
@@ -123,6 +124,12 @@ class GpuFrontEnd:
         g = Gates(int(bool(letterbox)), int(height), -big if min_height is None else float(min_height),
                   big if max_height is None else float(max_height), (C.c_float * 3)(*[float(a) for a in up]))
         _l.check(self._lib.flame_hip_frontend_set_gates(self._h, C.byref(g)), "flame_hip_frontend_set_gates")
+
+    def set_cost(self, zero_mean=True):
+        """The matching cost of the frames to come: COST_ZSSD (zero-mean: bit-invariant to a grey offset between the pose frame
+        and the current image -- auto-exposure cameras; wants win_size >= 7 on smooth imagery) or, `zero_mean=False`, COST_SSD
+        (the default).  May change between any two frames."""
+        _l.check(self._lib.flame_hip_frontend_set_cost(self._h, COST_ZSSD if zero_mean else COST_SSD), "flame_hip_frontend_set_cost")
 
     def _raw(self, raw):
         cam = getattr(self, "_cam", None)

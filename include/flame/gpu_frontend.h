@@ -27,6 +27,11 @@
 // (0, -1, 0): the reference's camera_world frame is right-down-forward [UPSTREAM-RECALL]); setGates() changes the gates later.  A
 // record the library refuses (min_height > max_height, a zero or non-finite up axis, ...) leaves its code in lastError() and
 // fails every track() until a valid one is set -- the gates are never dropped silently.
+//
+// MATCHING COST (flame_hip.h, flame_hip_frontend_set_cost; DESIGN.md 5.3 "Matching cost"): the constructor honours
+// Params::zero_mean_matching (this build's own switch: the zero-mean SSD, bit-invariant to a grey offset between the pose frame
+// and the current image); setZeroMean() changes it later, between any two frames.  With the switch off no call is made at all.  A
+// refusal lands in lastError() and fails every track() until a call succeeds, as with the gates.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -61,6 +66,10 @@ class GpuFrontEnd {
     gates_.max_height = params.max_height;
     gates_.up[0] = 0.f; gates_.up[1] = -1.f; gates_.up[2] = 0.f;
     if (handle_ && (gates_.letterbox || gates_.height_gate)) applyGates();  // (the reference's defaults: no call at all)
+    if (handle_ && params.zero_mean_matching) {  // (off: no call at all)
+      setZeroMean(true);
+      if (gates_error_) last_error_ = gates_error_;  // (a refused gate record stays what lastError() shows)
+    }
   }
   ~GpuFrontEnd() { flame_hip_frontend_destroy(handle_); }
   GpuFrontEnd(const GpuFrontEnd&) = delete;
@@ -113,6 +122,18 @@ class GpuFrontEnd {
   }
   const flame_hip_frontend_gates& gates() const { return gates_; }
 
+  // The matching cost of the frames to come: the zero-mean SSD (true) or the plain SSD (false, the default).  May change between
+  // any two frames: the feature state holds no cost.  false (lastError()) when the library refuses; track() then fails until a
+  // call succeeds.
+  bool setZeroMean(bool on) {
+    if (!handle_) return false;
+    cost_error_ = flame_hip_frontend_set_cost(handle_, on ? FLAME_HIP_FE_COST_ZSSD : FLAME_HIP_FE_COST_SSD);
+    last_error_ = cost_error_;
+    if (!cost_error_) zero_mean_ = on;
+    return cost_error_ == 0;
+  }
+  bool zeroMean() const { return zero_mean_; }
+
   // The ingest stage alone (flame_hip_frontend_rectify): `out` becomes the width x height rectified image of `raw`; the
   // feature state is untouched.
   bool rectify(const Image1b& raw, Image1b* out) {
@@ -155,6 +176,7 @@ class GpuFrontEnd {
   bool track(const FrameInput& in, FeatureSet* out) {
     if (!handle_) return false;  // (lastError() still holds why the handle could not be made)
     if (gates_error_) return fail(gates_error_);  // (a refused gate record is not tracked around)
+    if (cost_error_) return fail(cost_error_);    // (nor a refused matching cost)
     rectified_valid_ = false;
     const int rows = have_camera_ ? raw_height_ : height_, cols = have_camera_ ? raw_width_ : width_;
     if (!in.img || !out || in.img->rows != rows || in.img->cols != cols) return fail(FLAME_HIP_ERR_ARG);
@@ -234,6 +256,8 @@ class GpuFrontEnd {
   flame_hip_frontend_params fparams_;
   flame_hip_frontend_gates gates_;
   int gates_error_ = 0;  // what the library said to the last gate record
+  bool zero_mean_ = false;
+  int cost_error_ = 0;   // ... and to the last matching cost
   flame_hip_frontend* handle_ = nullptr;
   int last_error_ = 0;
 };

@@ -70,6 +70,12 @@ struct Params {
   // src/utils.cc:138-139) and `photo_pixels`, the number of pixels evaluated.  update() only (updateGraph() has neither image
   // nor pose).  Off by default: with it off update() makes exactly the calls it made before and none of the keys appears.
   bool photo_error = false;
+  // (this build's own) the matching cost of flame::GpuFrontEnd's epipolar search (gpu_frontend.h; DESIGN.md 5.3 "Matching cost"):
+  // true = zero-mean SSD (flame_hip_frontend_set_cost, FLAME_HIP_FE_COST_ZSSD), which a grey offset between a pose frame and the
+  // images tracked against it cannot move -- for cameras with auto-exposure (TUM's Kinect, EuRoC); use zparams.win_size >= 7 with
+  // it.  Gain is not removed.  Off by default: with it off the front end makes exactly the calls it made before.  Any other
+  // registered FrontEnd gets the field carried and has to honour it itself.
+  bool zero_mean_matching = false;
   // features (:209-231)
   // do_letterbox ("Process only middle third of image"): honoured by flame::GpuFrontEnd (gpu_frontend.h; DESIGN.md 5.3 "Gates")
   bool do_letterbox = false;

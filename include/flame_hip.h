@@ -508,7 +508,8 @@ typedef struct {
   int32_t max_dropouts;       /* Params::max_dropouts (5): a feature dies when it fails more often than this in a row */
   float idepth_min, idepth_max; /* search interval clamp (0.01, 10) */
   float idepth_init, var_init;  /* prior of a new feature (0.5, 0.25) */
-  float max_match_error;        /* grey^2 per window pixel above which the best match is rejected (100) */
+  float max_match_error;        /* grey^2 per window pixel above which the best match is rejected (100); with the ZSSD cost
+                                 * (flame_hip_frontend_set_cost) it bounds the residual's variance per pixel, not its mean square */
 } flame_hip_frontend_params;
 /* status of a feature in its last frame; the first four failures are in the order they are tested */
 enum {
@@ -549,7 +550,8 @@ int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* 
  * "died"; "detections_dropped" (no free slot), "max_features"; "camera" (1 = a camera is set), "ingest_device_us" (HIP events
  * around the raw upload and the ingest stage of the last _track_raw / _rectify; 0 after a _track), "ingest_raw_bytes" (what that
  * call uploaded); "gates" (bit 0 = letterbox, bit 1 = height band: what _set_gates last set), "held_height" / "refused_letterbox"
- * (features of the last frame the height band held / whose projection the letterbox refused) */
+ * (features of the last frame the height band held / whose projection the letterbox refused); "cost_mode" (FLAME_HIP_FE_COST_*:
+ * what _set_cost last set) */
 int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value);
 /* Debug/test hook: every slot's state (max_features entries each; any pointer may be NULL): alive, reference pixel (u, v),
  * ring slot of its pose frame, prior (mu, var) in the pose frame, dropout counter, last status (-1 = free), last best sample. */
@@ -636,6 +638,21 @@ typedef struct {
   float up[3];
 } flame_hip_frontend_gates;
 int flame_hip_frontend_set_gates(flame_hip_frontend* fe, const flame_hip_frontend_gates* gates /* NULL = none */);
+
+/* ---- matching cost (opt-in): what the tracker minimises along the epipolar segment (DESIGN.md 5.3 "Matching cost"; restated in
+ * tests/fe_zm_ref.py, which the GPU equals bit for bit).  With D_i = sum of the bilinear weights x current pixels - 256 x
+ * reference pixel over the n = win_size^2 window pixels (integers, |D_i| <= 65 280):
+ *   FLAME_HIP_FE_COST_SSD (the default):  C = sum D_i^2;                    BAD_MATCH when C > bad,
+ *   FLAME_HIP_FE_COST_ZSSD (zero-mean):   C = n sum D_i^2 - (sum D_i)^2;    BAD_MATCH when C > n bad (saturated at UINT64_MAX),
+ * with bad = (uint64)(max_match_error win_size^2 65536).  C replaces the SSD cost in every decision -- validity, argmin (ties to
+ * the smallest sample), BAD_MATCH, AMBIGUOUS, the sub-sample parabola -- and nothing else changes.  A grey offset between the
+ * pose frame and the current image that clips nowhere adds 256 b to every D_i and leaves the ZSSD cost the same integer: the
+ * whole tracker is bit-invariant to it (auto-exposure cameras).  A GAIN is not removed.  On very smooth imagery a small window
+ * cannot tell a shift along a ramp from an offset: use win_size >= 7 with ZSSD.
+ * Takes effect with the next _track / _track_raw and may change in mid-sequence (the feature state holds no cost).  Valid on a
+ * handle without a device.  Errors: ARG (NULL fe, unknown mode). */
+enum { FLAME_HIP_FE_COST_SSD = 0, FLAME_HIP_FE_COST_ZSSD = 1 };
+int flame_hip_frontend_set_cost(flame_hip_frontend* fe, int32_t mode);
 
 /* Debug/test hook (no device needed; works on a handle created with device = -1): copies the
  * named host-side plan array ("v_o2i", "e_o2i", "grow", "ginc", "eij", "tiles", "t_vmap",

@@ -12,7 +12,11 @@ wall time of the whole call, median over the pairs after a warm-up.
 along the default up axis, which holds about half of the features the letterbox leaves; only a third of the cells detect, so
 fewer features live) -- what the compares, the height and the held-cell flag cost where they act.
 
-    python tools/frontend_bench.py [--frames 100] [--warmup 10] [--gates]
+--zero-mean: the same pairs with the ZSSD matching cost (GpuFrontEnd.set_cost: k_fe_track<true>, one more integer sum per window
+pixel and a 64-bit multiply-subtract per sample).  --repeat N: N runs in one process, every run's tracking-frame device time,
+their median and their spread -- what DESIGN.md 6 compares between two trees.  --win-size N: the matching window (5; ZSSD wants 7).
+
+    python tools/frontend_bench.py [--frames 100] [--warmup 10] [--gates] [--zero-mean] [--win-size 7] [--repeat 5]
 """
 import argparse
 import json
@@ -37,7 +41,7 @@ def texture(h, w, seed=5, factor=8):
     return np.floor(up + 0.5).astype(np.uint8)
 
 
-def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False):
+def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=False, win_size=5):
     from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
     K = np.array([525, 0, 319.5, 0, 525, 239.5, 0, 0, 1], np.float32)
     big = texture(H, W + shift)
@@ -45,12 +49,14 @@ def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False):
     Ta = np.hstack([np.eye(3), np.zeros((3, 1))])
     Tb = Ta.copy()
     Tb[0, 3] = shift * 2.0 / 525.0  # the plane at depth 2 moved `shift` pixels
-    p = default_frontend_params()
+    p = default_frontend_params(win_size=win_size)
     t = {"poseframe": {"device": [], "host": []}, "tracking": {"device": [], "host": []}}
     with GpuFrontEnd(W, H, K, max_features=2048, max_poseframes=1) as fe:
         live = ok = held = refused = 0
         if gates:
             fe.set_gates(letterbox=True, min_height=-0.15, max_height=0.15)
+        if zero_mean:
+            fe.set_cost(zero_mean=True)
         for i in range(warmup + frames):
             for kind, img, T, pf in (("poseframe", a, Ta, True), ("tracking", b, Tb, False)):
                 fe.track(p, img, 2 * i + (not pf), T, pf)
@@ -63,6 +69,10 @@ def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False):
     res = {"width": W, "height": H, "live_features": live, "matched_ok": ok, "pairs": frames}
     if gates:
         res.update(gates=3, held_height=held, refused_letterbox=refused)
+    if zero_mean:
+        res.update(cost_mode=1)
+    if win_size != 5:
+        res.update(win_size=win_size)
     for kind in t:
         res[kind + "_device_us"] = float(np.median(t[kind]["device"]))
         res[kind + "_host_us"] = float(np.median(t[kind]["host"]))
@@ -74,5 +84,13 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--gates", action="store_true")
+    ap.add_argument("--zero-mean", action="store_true")
+    ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--win-size", type=int, default=5)
     a = ap.parse_args()
-    print(json.dumps({"frontend_track": run(max(a.frames, 50), a.warmup, gates=a.gates)}))
+    runs = [run(max(a.frames, 50), a.warmup, gates=a.gates, zero_mean=a.zero_mean, win_size=a.win_size) for _ in range(max(a.repeat, 1))]
+    res = runs[-1]
+    if a.repeat > 1:
+        t = [r["tracking_device_us"] for r in runs]
+        res.update(tracking_device_us_runs=t, tracking_device_us=float(np.median(t)), tracking_device_us_spread=[min(t), max(t)])
+    print(json.dumps({"frontend_track": res}))
