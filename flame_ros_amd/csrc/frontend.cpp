@@ -7,7 +7,9 @@
 // renders the Detections / Matches picture of the last tracked frame (frontend_debug.hip) from the record the tracker left on the
 // device.  flame_hip_frontend_set_gates records the letterbox and the height band; every frame forms the gate record of FeFrame
 // from them and the frame's pose.  flame_hip_frontend_set_cost records the matching cost (SSD / ZSSD); every frame forms the BAD_MATCH
-// threshold of that cost and picks the tracker's instantiation.  Reads no environment variable.
+// threshold of that cost and picks the tracker's instantiation.  flame_hip_frontend_set_ref_grad records the reference-patch gradient
+// gate; while it is on every frame forms the epipole table behind the pose table and runs the tracker's gated instantiation.  Reads
+// no environment variable.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -72,6 +74,8 @@ struct flame_hip_frontend {
   flame_hip_frontend_gates gates = {0, 0, 0.f, 0.f, {0.f, 0.f, 0.f}};
   // matching cost (set_cost): no state depends on it, so it may change between any two frames
   int32_t cost_mode = FLAME_HIP_FE_COST_SSD;
+  // reference-patch gradient gate (set_ref_grad): 0 = off; no state depends on it either
+  float min_epi_grad = 0.f;
 };
 
 namespace {
@@ -82,6 +86,9 @@ inline int hip_err(hipError_t e) { return e == hipSuccess ? 0 : FLAME_HIP_ERR_HI
     const hipError_t e_ = (x);         \
     if (e_ != hipSuccess) return hip_err(e_); \
   } while (0)
+
+// the pose table and, behind it, the epipole table: one allocation on each side, one upload while the gradient gate is on
+constexpr size_t kPoseBytes = sizeof(FePose) + sizeof(FeEpi);
 
 template <class T>
 T* carve(char*& p, size_t n) {
@@ -253,12 +260,12 @@ int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, i
   bool ok = hipStreamCreateWithFlags(&fe->stream, hipStreamNonBlocking) == hipSuccess && hipEventCreate(&fe->ev0) == hipSuccess &&
             hipEventCreate(&fe->ev1) == hipSuccess && hipEventCreate(&fe->evi0) == hipSuccess && hipEventCreate(&fe->evi1) == hipSuccess;
   ok = ok && hipMalloc(&fe->d_imgs, npix * (size_t)(max_poseframes + 1)) == hipSuccess &&
-       hipMalloc(&fe->d_poses, sizeof(FePose) * (size_t)max_poseframes) == hipSuccess && hipMalloc(&fe->d_state, state_bytes) == hipSuccess &&
+       hipMalloc(&fe->d_poses, kPoseBytes * (size_t)max_poseframes) == hipSuccess && hipMalloc(&fe->d_state, state_bytes) == hipSuccess &&
        hipMalloc(&fe->d_counts, sizeof(int32_t) * kFeCounts) == hipSuccess &&
-       hipHostMalloc(&fe->h_img, npix) == hipSuccess && hipHostMalloc(&fe->h_poses, sizeof(FePose) * (size_t)max_poseframes) == hipSuccess &&
+       hipHostMalloc(&fe->h_img, npix) == hipSuccess && hipHostMalloc(&fe->h_poses, kPoseBytes * (size_t)max_poseframes) == hipSuccess &&
        hipHostMalloc(&fe->h_counts, sizeof(int32_t) * kFeCounts) == hipSuccess && hipHostMalloc(&fe->h_out, sizeof(FeOut) * F) == hipSuccess;
   ok = ok && hipMemsetAsync(fe->d_state, 0, state_bytes, fe->stream) == hipSuccess &&
-       hipMemsetAsync(fe->d_poses, 0, sizeof(FePose) * (size_t)max_poseframes, fe->stream) == hipSuccess &&
+       hipMemsetAsync(fe->d_poses, 0, kPoseBytes * (size_t)max_poseframes, fe->stream) == hipSuccess &&
        hipStreamSynchronize(fe->stream) == hipSuccess;
   if (!ok) {
     release(fe);
@@ -279,6 +286,7 @@ int flame_hip_frontend_create(flame_hip_frontend** out, int device, int32_t W, i
   f.fx = K[0]; f.fy = K[4]; f.cx = K[2]; f.cy = K[5];
   f.imgs = fe->d_imgs;
   f.poses = fe->d_poses;
+  f.epi = reinterpret_cast<const FeEpi*>(fe->d_poses + max_poseframes);
   f.counts = fe->d_counts;
   *out = fe;
   return 0;
@@ -311,6 +319,8 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
   f.epipolar_line_var = params->epipolar_line_var;
   const bool zero_mean = fe->cost_mode == FLAME_HIP_FE_COST_ZSSD;
   f.bad_match_cost = bad_threshold(params->max_match_error, f.win, fe->cost_mode);
+  const bool ref_grad = fe->min_epi_grad > 0.f;
+  f.min_epi_grad = fe->min_epi_grad;
   f.is_poseframe = is_poseframe ? 1 : 0;
   f.gates = gate_record(fe, T_world_cam);
   const int32_t ncells = f.ncx * f.ncy;
@@ -340,6 +350,13 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
     if (fe->pf_used[p]) pose_record(fe->fx, fe->fy, fe->cx, fe->cy, T_world_cam, &fe->pf_T[12 * (size_t)p], &fe->h_poses[p]);
     else std::memset(&fe->h_poses[p], 0, sizeof(FePose));
   }
+  if (ref_grad) {
+    FeEpi* h_epi = reinterpret_cast<FeEpi*>(fe->h_poses + fe->max_poseframes);
+    for (int p = 0; p < fe->max_poseframes; ++p) {
+      if (fe->pf_used[p]) epipole_record(fe->fx, fe->fy, fe->cx, fe->cy, T_world_cam, &fe->pf_T[12 * (size_t)p], &h_epi[p]);
+      else std::memset(&h_epi[p], 0, sizeof(FeEpi));
+    }
+  }
   hipStream_t s = fe->stream;
   if (raw) {
     stage_raw(fe, img, pitch);
@@ -350,11 +367,11 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
     FE_HIP(hipEventRecord(fe->ev0, s));
     FE_HIP(hipMemcpyAsync(fe->d_imgs + (size_t)cur * npix, fe->h_img, npix, hipMemcpyHostToDevice, s));
   }
-  FE_HIP(hipMemcpyAsync(fe->d_poses, fe->h_poses, sizeof(FePose) * (size_t)fe->max_poseframes, hipMemcpyHostToDevice, s));
+  FE_HIP(hipMemcpyAsync(fe->d_poses, fe->h_poses, (ref_grad ? kPoseBytes : sizeof(FePose)) * (size_t)fe->max_poseframes, hipMemcpyHostToDevice, s));
   FE_HIP(hipMemsetAsync(fe->d_cell_key, 0xFF, (sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)ncells, s));
   FE_HIP(hipMemsetAsync(fe->d_counts, 0, sizeof(int32_t) * kFeCounts, s));
   if (overwrote) fe_launch_kill(s, f, valid_mask(fe));
-  fe_launch_track(s, f, zero_mean);
+  fe_launch_track(s, f, zero_mean, ref_grad);
   if (is_poseframe) fe_launch_detect(s, f);
   fe_launch_compact(s, f);
   FE_HIP(hipGetLastError());
@@ -457,6 +474,14 @@ int flame_hip_frontend_set_gates(flame_hip_frontend* fe, const flame_hip_fronten
 int flame_hip_frontend_set_cost(flame_hip_frontend* fe, int32_t mode) {
   if (!fe || (mode != FLAME_HIP_FE_COST_SSD && mode != FLAME_HIP_FE_COST_ZSSD)) return FLAME_HIP_ERR_ARG;
   fe->cost_mode = mode;  // takes effect with the next frame
+  return 0;
+}
+
+int flame_hip_frontend_set_ref_grad(flame_hip_frontend* fe, float min_grad) {
+  if (!fe) return FLAME_HIP_ERR_ARG;
+  if (!std::isfinite(min_grad)) return FLAME_HIP_ERR_NAN;
+  if (min_grad < 0.f) return FLAME_HIP_ERR_ARG;
+  fe->min_epi_grad = min_grad;  // takes effect with the next frame; 0 = off
   return 0;
 }
 
@@ -615,6 +640,8 @@ int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* va
   if (!std::strcmp(key, "debug_image_device_us")) { *value = (int64_t)(fe->debug_image_device_us + 0.5); return 0; }
   if (!std::strcmp(key, "gates")) { *value = (fe->gates.letterbox ? 1 : 0) | (fe->gates.height_gate ? 2 : 0); return 0; }
   if (!std::strcmp(key, "cost_mode")) { *value = fe->cost_mode; return 0; }
+  if (!std::strcmp(key, "ref_grad")) { *value = fe->min_epi_grad > 0.f ? 1 : 0; return 0; }
+  if (!std::strcmp(key, "fail_ref_grad")) { *value = fe->counts[12]; return 0; }
   if (!std::strcmp(key, "held_height")) { *value = fe->counts[10]; return 0; }
   if (!std::strcmp(key, "refused_letterbox")) { *value = fe->counts[11]; return 0; }
   if (!std::strcmp(key, "camera")) { *value = fe->have_cam ? 1 : 0; return 0; }

@@ -13,9 +13,10 @@ constexpr int kFeMaxPoseframes = 64;  // the ring's valid slots travel as one 64
 constexpr int kFeMaxWin = 9;
 
 // per-slot status of the last frame (FLAME_HIP_FE_* of include/flame_hip.h)
-enum { kFeOk = 0, kFeNoParallax = 1, kFeOutside = 2, kFeBadMatch = 3, kFeAmbiguous = 4, kFeNew = 5, kFeDied = 6, kFeFree = -1 };
-constexpr int kFeCounts = 16;  // counts[]: 0 = emitted, 1 = live, 2 + status = features of that status, 9 = detections dropped (no free slot),
-                               // 10 = features held by the height gate, 11 = projections refused by the letterbox
+enum { kFeOk = 0, kFeNoParallax = 1, kFeOutside = 2, kFeBadMatch = 3, kFeAmbiguous = 4, kFeNew = 5, kFeDied = 6, kFeRefGrad = 7, kFeFree = -1 };
+constexpr int kFeCounts = 16;  // counts[]: 0 = emitted, 1 = live, 2 + status = features of that status (0..6), 9 = detections dropped (no free slot),
+                               // 10 = features held by the height gate, 11 = projections refused by the letterbox,
+                               // 12 = features of status kFeRefGrad (2 + 7 is taken)
 
 // A = K R and c = K t of T_cur_ref, rounded once to float32 on the host (one record per pose-frame ring slot)
 struct FePose {
@@ -41,6 +42,25 @@ inline void pose_record(double fx, double fy, double cx, double cy, const double
   out->c[0] = (float)(fx * t[0] + cx * t[2]);
   out->c[1] = (float)(fy * t[1] + cy * t[2]);
   out->c[2] = (float)t[2];
+}
+
+// The epipole of the current view in a pose frame's image, homogeneous (DESIGN.md 5.3 "Reference-patch gradient"): with o = R_ref^T
+// (t_cur - t_ref) the current camera's centre in the reference frame, E = (fx o0 + cx o2, fy o1 + cy o2, o2).  One record per
+// pose-frame ring slot in a table of its own behind the pose table (FePose keeps its layout: predict.h shares it); formed and
+// uploaded only while the gate is on.
+struct FeEpi {
+  float E[3];
+};
+
+// E of T_world_cur = Tc seen from T_world_ref = Tr (row-major [R|t]), in double, sums left to right, each entry rounded once to
+// float32 (tests/fe_rg_ref.py epipole_record() is the same statement).
+inline void epipole_record(double fx, double fy, double cx, double cy, const double* Tc, const double* Tr, FeEpi* out) {
+  const double d0 = Tc[3] - Tr[3], d1 = Tc[7] - Tr[7], d2 = Tc[11] - Tr[11];
+  double o[3];
+  for (int i = 0; i < 3; ++i) o[i] = (Tr[0 * 4 + i] * d0 + Tr[1 * 4 + i] * d1) + Tr[2 * 4 + i] * d2;
+  out->E[0] = (float)(fx * o[0] + cx * o[2]);
+  out->E[1] = (float)(fy * o[1] + cy * o[2]);
+  out->E[2] = (float)o[2];
 }
 
 // one emitted feature (the frame's output record, compacted in ascending slot order)
@@ -91,10 +111,14 @@ struct FeFrame {
   float4* seg;     // {x0, y0, ex, ey}: sample k of the search sits at (x0 + k ex, y0 + k ey)
   int32_t* steps;  // S (0 = no search ran: free, NO_PARALLAX, OUTSIDE before the segment exists, NEW)
   FeGates gates;
+  // the reference-patch gradient gate (read by the RG instantiations of k_fe_track only): min_grad, and the epipole table
+  float min_epi_grad;
+  const FeEpi* epi;
 };
 
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask);
-void fe_launch_track(hipStream_t s, const FeFrame& f, bool zero_mean);  // zero_mean: the ZSSD cost (f.bad_match_cost is that cost's threshold)
+// zero_mean: the ZSSD cost (f.bad_match_cost is that cost's threshold); ref_grad: the reference-patch gradient gate (f.min_epi_grad, f.epi)
+void fe_launch_track(hipStream_t s, const FeFrame& f, bool zero_mean, bool ref_grad);
 void fe_launch_detect(hipStream_t s, const FeFrame& f);
 void fe_launch_compact(hipStream_t s, const FeFrame& f);
 

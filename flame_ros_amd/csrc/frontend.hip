@@ -76,6 +76,41 @@ __device__ __forceinline__ unsigned long long fe_cost(const FeFrame& f, const ui
   return C;
 }
 
+// The reference-patch gradient gate (DESIGN.md 5.3 "Reference-patch gradient"): does the win x win reference window have structure
+// ALONG the epipolar line?  The 64 lanes cover the n <= 81 window pixels in two passes; the three sums of the structure tensor are
+// integers (each <= 81 * 255^2 < 2^24: exact as float32) and an xor butterfly leaves them in every lane, so the result is
+// wave-uniform.  (dx, dy) is the direction from the feature's pixel to the current view's epipole, homogeneous: no division, the
+// sign does not matter.  Passes iff Q >= thr N, i.e. the mean square of the directional derivative is at least min_grad^2 (a
+// central difference is twice the gradient); a NaN refuses.  kFeOutside when the one-pixel ring around the window leaves the image.
+__device__ __forceinline__ int fe_ref_grad(const FeFrame& f, const uint8_t* __restrict__ ref, int p, int u, int v, int lane) {
+  const int r = f.win >> 1, n = f.win * f.win;
+  if (u - r - 1 < 0 || v - r - 1 < 0 || u + r + 1 > f.W - 1 || v + r + 1 > f.H - 1) return kFeOutside;
+  int sxx = 0, sxy = 0, syy = 0;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int i = lane + 64 * pass;
+    if (i < n) {
+      const uint8_t* __restrict__ q = ref + (size_t)(v - r + i / f.win) * f.W + (u - r + i % f.win);
+      const int gx = (int)q[1] - (int)q[-1], gy = (int)q[f.W] - (int)q[-f.W];
+      sxx += gx * gx;
+      sxy += gx * gy;
+      syy += gy * gy;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sxx += __shfl_xor(sxx, o, 64);
+    sxy += __shfl_xor(sxy, o, 64);
+    syy += __shfl_xor(syy, o, 64);
+  }
+  const FeEpi e = f.epi[p];
+  const float dx = e.E[0] - (float)u * e.E[2], dy = e.E[1] - (float)v * e.E[2];
+  const float Q = ((dx * dx) * (float)sxx + (2.0f * (dx * dy)) * (float)sxy) + (dy * dy) * (float)syy;
+  const float N = dx * dx + dy * dy;
+  const float thr = (4.0f * (float)n) * (f.min_epi_grad * f.min_epi_grad);
+  return Q >= thr * N ? kFeOk : kFeRefGrad;
+}
+
 __global__ __launch_bounds__(256) void k_fe_kill(FeFrame f, unsigned long long valid_mask) {
   const int slot = blockIdx.x * 256 + threadIdx.x;
   if (slot >= f.max_features) return;
@@ -83,8 +118,9 @@ __global__ __launch_bounds__(256) void k_fe_kill(FeFrame f, unsigned long long v
 }
 
 // ZM picks the matching cost (false: SSD, true: ZSSD); f.bad_match_cost is the host's threshold for that cost.  Everything
-// behind the cost -- argmin, BAD_MATCH, AMBIGUOUS, the parabola -- takes it as it comes.
-template <bool ZM>
+// behind the cost -- argmin, BAD_MATCH, AMBIGUOUS, the parabola -- takes it as it comes.  RG puts the reference-patch gradient
+// gate between the NO_PARALLAX test and the search; the instantiations without it hold none of its code.
+template <bool ZM, bool RG>
 __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
   const int lane = threadIdx.x & 63;
   const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -129,8 +165,11 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
     const float x1 = (a0 + xi1 * c0) / d1, y1 = (a1 + xi1 * c1) / d1;
     const float dx = x1 - x0, dy = y1 - y0;
     const float L = sqrtf(dx * dx + dy * dy);
+    int rg = kFeOk;
     if (!(L >= 2.0f)) {
       status = kFeNoParallax;
+    } else if (RG && (rg = fe_ref_grad(f, ref, p, u, v, lane)) != kFeOk) {
+      status = rg;  // no structure along the epipolar line (or the window's ring leaves the image): no search, a failure
     } else {
       const int S = L >= (float)kFeMaxSamples ? kFeMaxSamples : (int)ceilf(L);
       const float ex = dx / (float)S, ey = dy / (float)S;
@@ -222,7 +261,7 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
     }
   }
 
-  const bool failed = status == kFeOutside || status == kFeBadMatch || status == kFeAmbiguous;
+  const bool failed = status == kFeOutside || status == kFeBadMatch || status == kFeAmbiguous || (RG && status == kFeRefGrad);
   if (status == kFeOk) {
     mu = mu_new;
     var = var_new;
@@ -253,7 +292,7 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
     f.kstar[slot] = ks;
     f.seg[slot] = seg;
     f.steps[slot] = steps;
-    atomicAdd(&f.counts[2 + status], 1);
+    atomicAdd(&f.counts[RG && status == kFeRefGrad ? 12 : 2 + status], 1);
     if (refused) atomicAdd(&f.counts[11], 1);
     if (dies) {
       f.alive[slot] = 0;
@@ -415,9 +454,15 @@ __global__ __launch_bounds__(1024) void k_fe_compact(FeFrame f) {
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask) {
   hipLaunchKernelGGL(k_fe_kill, dim3((f.max_features + 255) / 256), dim3(256), 0, s, f, valid_mask);
 }
-void fe_launch_track(hipStream_t s, const FeFrame& f, bool zero_mean) {
-  if (zero_mean) hipLaunchKernelGGL(k_fe_track<true>, dim3((f.max_features + 3) / 4), dim3(256), 0, s, f);
-  else hipLaunchKernelGGL(k_fe_track<false>, dim3((f.max_features + 3) / 4), dim3(256), 0, s, f);
+void fe_launch_track(hipStream_t s, const FeFrame& f, bool zero_mean, bool ref_grad) {
+  const dim3 grid((f.max_features + 3) / 4), block(256);
+  if (ref_grad) {
+    if (zero_mean) hipLaunchKernelGGL((k_fe_track<true, true>), grid, block, 0, s, f);
+    else hipLaunchKernelGGL((k_fe_track<false, true>), grid, block, 0, s, f);
+  } else {
+    if (zero_mean) hipLaunchKernelGGL((k_fe_track<true, false>), grid, block, 0, s, f);
+    else hipLaunchKernelGGL((k_fe_track<false, false>), grid, block, 0, s, f);
+  }
 }
 void fe_launch_detect(hipStream_t s, const FeFrame& f) {
   hipLaunchKernelGGL(k_fe_detect, dim3((f.ncx * f.ncy + 3) / 4), dim3(256), 0, s, f);

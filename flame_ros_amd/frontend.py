@@ -12,6 +12,7 @@ from . import lib as _l
 from .lib import FlameHipError  # noqa: F401
 
 FE_OK, FE_NO_PARALLAX, FE_OUTSIDE, FE_BAD_MATCH, FE_AMBIGUOUS, FE_NEW, FE_DIED, FE_FREE = 0, 1, 2, 3, 4, 5, 6, -1
+REF_GRAD = FE_REF_GRAD = 7  # FLAME_HIP_FE_REF_GRAD: refused by the reference-patch gradient gate (set_ref_grad); info key "fail_ref_grad"
 COST_SSD, COST_ZSSD = 0, 1  # FLAME_HIP_FE_COST_*: the matching cost (set_cost)
 STATUS_KEYS = ("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died")
 IMG_DETECTIONS, IMG_MATCHES = _l.FE_IMG_DETECTIONS, _l.FE_IMG_MATCHES  # FLAME_HIP_FE_IMG_*
@@ -130,6 +131,12 @@ class GpuFrontEnd:
         and the current image -- auto-exposure cameras; wants win_size >= 7 on smooth imagery) or, `zero_mean=False`, COST_SSD
         (the default).  May change between any two frames."""
         _l.check(self._lib.flame_hip_frontend_set_cost(self._h, COST_ZSSD if zero_mean else COST_SSD), "flame_hip_frontend_set_cost")
+
+    def set_ref_grad(self, min_grad):
+        """The reference-patch gradient gate of the frames to come: a feature whose reference window has a root-mean-square grey
+        gradient below `min_grad` ALONG its epipolar line (an edge parallel to the line: the aperture problem) is not searched and
+        gets status REF_GRAD, a failure like AMBIGUOUS.  0 (the default) switches it off.  May change between any two frames."""
+        _l.check(self._lib.flame_hip_frontend_set_ref_grad(self._h, float(min_grad)), "flame_hip_frontend_set_ref_grad")
 
     def _raw(self, raw):
         cam = getattr(self, "_cam", None)

@@ -32,6 +32,12 @@
 // Params::zero_mean_matching (this build's own switch: the zero-mean SSD, bit-invariant to a grey offset between the pose frame
 // and the current image); setZeroMean() changes it later, between any two frames.  With the switch off no call is made at all.  A
 // refusal lands in lastError() and fails every track() until a call succeeds, as with the gates.
+//
+// REFERENCE-PATCH GRADIENT (flame_hip.h, flame_hip_frontend_set_ref_grad; DESIGN.md 5.3 "Reference-patch gradient"): the constructor
+// honours Params::min_epipolar_grad (this build's own switch: a feature whose reference window has no structure along its epipolar
+// line is not searched); setRefGrad() changes it later, between any two frames.  With the switch at 0 no call is made at all and
+// `num_fail_ref_patch_grad` stays unset.  A refusal (a negative or non-finite value) lands in lastError() and fails every track()
+// until a call succeeds.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -69,6 +75,11 @@ class GpuFrontEnd {
     if (handle_ && params.zero_mean_matching) {  // (off: no call at all)
       setZeroMean(true);
       if (gates_error_) last_error_ = gates_error_;  // (a refused gate record stays what lastError() shows)
+    }
+    if (handle_ && params.min_epipolar_grad != 0.f) {  // (off: no call at all)
+      const int before = last_error_;
+      setRefGrad(params.min_epipolar_grad);
+      if (before) last_error_ = before;  // (an earlier refusal stays what lastError() shows)
     }
   }
   ~GpuFrontEnd() { flame_hip_frontend_destroy(handle_); }
@@ -134,6 +145,18 @@ class GpuFrontEnd {
   }
   bool zeroMean() const { return zero_mean_; }
 
+  // The reference-patch gradient gate of the frames to come: the smallest root-mean-square grey gradient along the epipolar line a
+  // reference window needs to be searched; 0 = off (the default).  May change between any two frames.  false (lastError()) when
+  // the library refuses the value (negative, non-finite): the gate stays what it was and track() fails until a call succeeds.
+  bool setRefGrad(float min_grad) {
+    if (!handle_) return false;
+    ref_grad_error_ = flame_hip_frontend_set_ref_grad(handle_, min_grad);
+    last_error_ = ref_grad_error_;
+    if (!ref_grad_error_) min_epipolar_grad_ = min_grad;
+    return ref_grad_error_ == 0;
+  }
+  float refGrad() const { return min_epipolar_grad_; }
+
   // The ingest stage alone (flame_hip_frontend_rectify): `out` becomes the width x height rectified image of `raw`; the
   // feature state is untouched.
   bool rectify(const Image1b& raw, Image1b* out) {
@@ -177,6 +200,7 @@ class GpuFrontEnd {
     if (!handle_) return false;  // (lastError() still holds why the handle could not be made)
     if (gates_error_) return fail(gates_error_);  // (a refused gate record is not tracked around)
     if (cost_error_) return fail(cost_error_);    // (nor a refused matching cost)
+    if (ref_grad_error_) return fail(ref_grad_error_);  // (nor a refused gradient gate)
     rectified_valid_ = false;
     const int rows = have_camera_ ? raw_height_ : height_, cols = have_camera_ ? raw_width_ : width_;
     if (!in.img || !out || in.img->rows != rows || in.img->cols != cols) return fail(FLAME_HIP_ERR_ARG);
@@ -213,8 +237,8 @@ class GpuFrontEnd {
 
   // The tracking stats FlameStats carries (reference src/utils.cc:124-129), from the counts of the frame just tracked
   // (flame_hip_frontend_info): features whose idepth was updated, features that died of too many dropouts, ambiguous matches,
-  // matches above the cost threshold.  `num_fail_max_var` is Flame's own (its variance gate); `num_fail_ref_patch_grad` has no
-  // counterpart in this front end's statement (DESIGN.md 5.3 tests no reference-patch gradient) and stays unset.
+  // matches above the cost threshold.  `num_fail_max_var` is Flame's own (its variance gate); `num_fail_ref_patch_grad` is
+  // the features the reference-patch gradient gate refused and is set only while that gate is on (it is off by default: unset).
   void reportStats(utils::StatsTracker* stats) const {
     if (!handle_ || !stats) return;
     static const char* const kKeys[4][2] = {{"num_idepth_updates", "ok"}, {"num_fail_max_dropouts", "died"},
@@ -228,6 +252,9 @@ class GpuFrontEnd {
     if (flame_hip_frontend_info(handle_, "gates", &g) == 0 && g != 0) {
       if (flame_hip_frontend_info(handle_, "held_height", &v) == 0) stats->set("num_held_height", static_cast<double>(v));
       if (flame_hip_frontend_info(handle_, "refused_letterbox", &v) == 0) stats->set("num_refused_letterbox", static_cast<double>(v));
+    }
+    if (flame_hip_frontend_info(handle_, "ref_grad", &g) == 0 && g != 0) {
+      if (flame_hip_frontend_info(handle_, "fail_ref_grad", &v) == 0) stats->set("num_fail_ref_patch_grad", static_cast<double>(v));
     }
   }
 
@@ -258,6 +285,8 @@ class GpuFrontEnd {
   int gates_error_ = 0;  // what the library said to the last gate record
   bool zero_mean_ = false;
   int cost_error_ = 0;   // ... and to the last matching cost
+  float min_epipolar_grad_ = 0.f;
+  int ref_grad_error_ = 0;  // ... and to the last gradient gate
   flame_hip_frontend* handle_ = nullptr;
   int last_error_ = 0;
 };

@@ -76,6 +76,13 @@ struct Params {
   // it.  Gain is not removed.  Off by default: with it off the front end makes exactly the calls it made before.  Any other
   // registered FrontEnd gets the field carried and has to honour it itself.
   bool zero_mean_matching = false;
+  // (this build's own) the reference-patch gradient gate of flame::GpuFrontEnd's tracker (gpu_frontend.h; DESIGN.md 5.3
+  // "Reference-patch gradient"; flame_hip_frontend_set_ref_grad): a feature whose reference window has a root-mean-square grey
+  // gradient below this ALONG its epipolar line -- an edge parallel to the line, the aperture problem -- is not searched in that
+  // frame and fails like an ambiguous match; `num_fail_ref_patch_grad` counts them.  The scale is min_grad_mag's (5 is a fair
+  // choice).  0 = off, the default: with it off the front end makes exactly the calls it made before and the key stays unset.
+  // Any other registered FrontEnd gets the field carried and has to honour it itself.
+  float min_epipolar_grad = 0.f;
   // features (:209-231)
   // do_letterbox ("Process only middle third of image"): honoured by flame::GpuFrontEnd (gpu_frontend.h; DESIGN.md 5.3 "Gates")
   bool do_letterbox = false;

@@ -519,7 +519,9 @@ enum {
   FLAME_HIP_FE_BAD_MATCH = 3,   /* best cost above max_match_error (or a degenerate measurement) */
   FLAME_HIP_FE_AMBIGUOUS = 4,   /* a sample more than 2 steps from the best costs less than 1.5 x the best */
   FLAME_HIP_FE_NEW = 5,         /* detected in this (pose) frame */
-  FLAME_HIP_FE_DIED = 6         /* dropout counter exceeded max_dropouts in this frame: the slot is free again */
+  FLAME_HIP_FE_DIED = 6,        /* dropout counter exceeded max_dropouts in this frame: the slot is free again */
+  FLAME_HIP_FE_REF_GRAD = 7     /* only with flame_hip_frontend_set_ref_grad: the reference patch has no structure along the epipolar
+                                 * line; no search ran, a failure like AMBIGUOUS (tested after NO_PARALLAX, before the search) */
 };
 void flame_hip_frontend_default_params(flame_hip_frontend_params* p);
 /* K row-major 3x3 pinhole (fx = K[0], fy = K[4], cx = K[2], cy = K[5]); images arrive rectified unless a camera is set
@@ -551,7 +553,8 @@ int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* 
  * around the raw upload and the ingest stage of the last _track_raw / _rectify; 0 after a _track), "ingest_raw_bytes" (what that
  * call uploaded); "gates" (bit 0 = letterbox, bit 1 = height band: what _set_gates last set), "held_height" / "refused_letterbox"
  * (features of the last frame the height band held / whose projection the letterbox refused); "cost_mode" (FLAME_HIP_FE_COST_*:
- * what _set_cost last set) */
+ * what _set_cost last set); "ref_grad" (1 while the gate of _set_ref_grad is on), "fail_ref_grad" (features of the last frame with
+ * status REF_GRAD) */
 int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value);
 /* Debug/test hook: every slot's state (max_features entries each; any pointer may be NULL): alive, reference pixel (u, v),
  * ring slot of its pose frame, prior (mu, var) in the pose frame, dropout counter, last status (-1 = free), last best sample. */
@@ -653,6 +656,22 @@ int flame_hip_frontend_set_gates(flame_hip_frontend* fe, const flame_hip_fronten
  * handle without a device.  Errors: ARG (NULL fe, unknown mode). */
 enum { FLAME_HIP_FE_COST_SSD = 0, FLAME_HIP_FE_COST_ZSSD = 1 };
 int flame_hip_frontend_set_cost(flame_hip_frontend* fe, int32_t mode);
+
+/* ---- reference-patch gradient gate (opt-in): an edge parallel to the epipolar line slides along itself, every sample of the search
+ * costs about the same and the minimum that gets fused is noise (the aperture problem).  With min_grad > 0 the tracker asks, after
+ * the NO_PARALLAX test and before the search, whether the feature's win x win reference window has structure ALONG the line
+ * (DESIGN.md 5.3 "Reference-patch gradient"; restated in tests/fe_rg_ref.py, which the GPU equals bit for bit):
+ *   E = K o (homogeneous, formed in double on the host, rounded once to float32), o = R_ref^T (t_cur - t_ref): the epipole of the
+ *     current view in the pose frame's image; (dx, dy) = (E0 - u E2, E1 - v E2) at the feature's pixel (u, v);
+ *   Sxx, Sxy, Syy = the integer sums of gx^2, gx gy, gy^2 over the window, gx = I(x+1, y) - I(x-1, y), gy = I(x, y+1) - I(x, y-1);
+ *   the feature passes iff  dx^2 Sxx + 2 dx dy Sxy + dy^2 Syy >= 4 win^2 min_grad^2 (dx^2 + dy^2)  (float32, each operation
+ *     rounded on its own; a NaN refuses): the mean square of the patch's derivative along the line is at least min_grad^2.
+ * A refused feature gets status FLAME_HIP_FE_REF_GRAD: no search, prior and k* = -1 untouched, search record zero, one dropout.  If
+ * the one-pixel ring around the window leaves the image (win_size grew after the detection) the status is OUTSIDE.
+ * min_grad = 0 (the default): off, every call does what it did before.  Takes effect with the next _track / _track_raw and may
+ * change in mid-sequence.  Valid on a handle without a device.  Errors: NAN (non-finite), ARG (NULL fe, negative); after a refusal
+ * the setting is what it was.  Info keys "ref_grad", "fail_ref_grad". */
+int flame_hip_frontend_set_ref_grad(flame_hip_frontend* fe, float min_grad);
 
 /* Debug/test hook (no device needed; works on a handle created with device = -1): copies the
  * named host-side plan array ("v_o2i", "e_o2i", "grow", "ginc", "eij", "tiles", "t_vmap",
