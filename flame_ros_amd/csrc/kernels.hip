@@ -1443,7 +1443,7 @@ __global__ __launch_bounds__(256) void k_raster_fill(int32_t width, int32_t heig
 // ------------------------------------------------------------------------------------------
 // Debug images of flame::Flame (reference src/flame_offline_tum.cc:731-766; what each shows:
 // cfg/flame_offline_tum.yaml:58-64), rendered on the device into a BGR8 buffer so that update()
-// never draws on the host; the rules are stated in oracle/nltgv2_oracle.c (nltgv2_debug_image).
+// never draws on the host; the rules are stated in oracle/nltgv2_oracle.c (the block above nltgv2_coverage).
 // "Later primitive overwrites earlier ones" is made order-free by a key map: every primitive
 // atomicMax-es its index + 1 into the pixels it covers, a second pass colours each pixel from the
 // winning primitive.
@@ -1459,7 +1459,15 @@ __device__ __forceinline__ void put_jet(uint8_t* o, float v) {  // jet(v, 0, 2),
   o[1] = (uint8_t)(255.0f * g + 0.5f);
   o[2] = (uint8_t)(255.0f * r + 0.5f);
 }
-__device__ __forceinline__ int round_px(float v) { return (int)(v + (v >= 0.0f ? 0.5f : -0.5f)); }
+// Pixel of a coordinate the caller has found in reach (so |v| fits an int): half away from zero, exactly
+// (|v| - floorf(|v|) is exact in float32; v + 0.5f is not: 0.5 - 2^-25 would tie up to 1.0f).
+__device__ __forceinline__ int round_px(float v) {
+  const float a = fabsf(v), f = floorf(a);
+  const int n = (int)f + ((a - f) >= 0.5f ? 1 : 0);
+  return v < 0.0f ? -n : n;
+}
+// Reach of a side's end point coordinate, R = W + H: compared in float, so a NaN is out of reach.
+__device__ __forceinline__ bool in_reach(float c, int R) { return c >= -(float)R && c <= (float)(2 * R); }
 
 // one thread per triangle side: Bresenham between the rounded end points
 __global__ __launch_bounds__(256) void k_dbg_lines(int32_t T, int32_t W, int32_t H, const float2* __restrict__ pos,
@@ -1470,6 +1478,7 @@ __global__ __launch_bounds__(256) void k_dbg_lines(int32_t T, int32_t W, int32_t
   const int32_t t = i / 3, k = i - 3 * t;
   if (!tri_valid[t]) return;
   const float2 pa = pos[tris[3 * t + k]], pb = pos[tris[3 * t + (k + 1) % 3]];
+  if (!(in_reach(pa.x, W + H) && in_reach(pa.y, W + H) && in_reach(pb.x, W + H) && in_reach(pb.y, W + H))) return;
   int x0 = round_px(pa.x), y0 = round_px(pa.y);
   const int x1 = round_px(pb.x), y1 = round_px(pb.y);
   const int dx = abs(x1 - x0), dy = -abs(y1 - y0);
@@ -1503,7 +1512,9 @@ __global__ __launch_bounds__(256) void k_dbg_feat_mark(int32_t n, int32_t W, int
                                                        uint32_t* __restrict__ key) {
   const int32_t f = blockIdx.x * 256 + threadIdx.x;
   if (f >= n) return;
-  const int px = round_px(feat[3 * f]), py = round_px(feat[3 * f + 1]);
+  const float fu = feat[3 * f], fv = feat[3 * f + 1];
+  if (!(fu > -2.0f && fu < (float)(W + 1) && fv > -2.0f && fv < (float)(H + 1))) return;
+  const int px = round_px(fu), py = round_px(fv);
   for (int dy = -1; dy <= 1; ++dy)
     for (int dx = -1; dx <= 1; ++dx) {
       const int x = px + dx, y = py + dy;

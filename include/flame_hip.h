@@ -270,7 +270,11 @@ int flame_hip_frame_results(flame_hip_graph* g, const flame_hip_params* p, float
  * idepth; NORMALS: "image colored by interpolated normal vectors" over the filtered dense map;
  * IDEPTHMAP: jet of the filtered dense idepthmap.  Colour = jet(idepth * scene_color_scale, 0, 2)
  * (output/scene_color_scale, cfg/flame_offline_tum.yaml:35).  The exact rules are stated in
- * oracle/nltgv2_oracle.c (nltgv2_debug_image).  Nothing is drawn on the host; the dense raster is
+ * oracle/nltgv2_oracle.c (the block above nltgv2_coverage).  Positions need no validation by the
+ * caller: a coordinate becomes a pixel by exact half-away-from-zero rounding, and only after a float
+ * test of its reach -- a triangle side is drawn iff all four coordinates of its end points lie in
+ * [-(W + H), 2 (W + H)], a feature iff -2 < u < W + 1 and -2 < v < H + 1 -- so NaN, infinite and huge
+ * positions draw nothing.  Nothing is drawn on the host; the dense raster is
  * shared with flame_hip_frame_results' coverage and flame_hip_depthmaps.  Synchronises. */
 enum { FLAME_HIP_IMG_WIREFRAME = 0, FLAME_HIP_IMG_FEATURES = 1, FLAME_HIP_IMG_NORMALS = 2, FLAME_HIP_IMG_IDEPTHMAP = 3 };
 int flame_hip_debug_image(flame_hip_graph* g, int32_t kind, const float Kinv[9],

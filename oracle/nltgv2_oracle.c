@@ -463,13 +463,29 @@ void nltgv2_depth_and_cloud(int32_t width, int32_t height, const float* idepthma
  * is not kept), W x H, row-major.
  *   coverage  : (number of pixels of the FILTERED dense idepthmap that are not NaN) / (W * H),
  *               one float32 division of the two integers converted to float32
- *   colour(id): jet(id * scene_color_scale, 0, 2) -- include/flame/utils/visualization.h jet()
- *   wireframe : for every valid triangle t in ascending t, sides k = 0,1,2 (vertices tris[3t+k],
- *               tris[3t+(k+1)%3]): Bresenham line between the rounded (half away from zero)
- *               vertex positions, clipped per pixel, colour(0.5 * (x_a + x_b)); later lines
- *               overwrite earlier ones
- *   features  : for every raw feature f in ascending f a 3x3 square around its rounded position,
- *               colour(mu_f); later features overwrite earlier ones
+ *   colour(id): jet(id * scene_color_scale, 0, 2) -- include/flame/utils/visualization.h jet():
+ *               t = clamp(p / 2, 0, 1) of the float32 product p, channel c = clamp(1.5 - |4 t - k|, 0, 1)
+ *               with k = 1 (B), 2 (G), 3 (R), stored as floor(255 c + 0.5).  p below 0 and -inf read as
+ *               t = 0, BGR (128, 0, 0); p above 2, +inf and NaN as t = 1, BGR (0, 0, 128)
+ *   pixel(c)  : the coordinate rounded half away from zero, EXACTLY: floor(|c|), plus one where the
+ *               (exact) remainder |c| - floor(|c|) is >= 0.5, with the sign of c.  (Not c + 0.5f
+ *               truncated: that sum rounds, so the float32 predecessor of 0.5 would land on 1.)
+ *   reach     : with R = W + H a coordinate c is in reach iff c >= -(float)R && c <= (float)(2 * R),
+ *               compared in float BEFORE any conversion to int (NaN, infinite and huge values fail;
+ *               converting them is undefined).  A side is drawn iff all four coordinates of its two
+ *               end points are in reach; otherwise no pixel of it is.  In reach a walk has at most
+ *               3 R + 1 pixels, so the 4 R guard of the loop never cuts a line: it is a backstop only.
+ *   wireframe : for every valid triangle t in ascending t, sides k = 0,1,2 (vertices a = tris[3t+k],
+ *               b = tris[3t+(k+1)%3]) in reach: Bresenham line from pixel(a) to pixel(b), both
+ *               included, clipped per pixel, colour(0.5 * (x_a + x_b)); later lines overwrite earlier
+ *               ones (the largest 3 t + k wins a pixel).  The walk, all in integers: dx = |x1 - x0|,
+ *               dy = -|y1 - y0|, err = dx + dy; at each pixel e2 = 2 err; x steps iff e2 >= dy (then
+ *               err += dy), y steps iff e2 <= dx (then err += dx), both tests on the same e2 -- a tie
+ *               steps, so a line of slope 1/2 or 2 depends on the end it starts from
+ *   features  : for every raw feature f in ascending f with u > -2 && u < W + 1 && v > -2 && v < H + 1
+ *               (compared in float; everything else has no pixel in the image, NaN included) a 3x3
+ *               square around (pixel(u), pixel(v)), clipped per pixel, colour(mu_f); later features
+ *               overwrite earlier ones (the largest f wins a pixel)
  *   idepthmap : colour(idepthmap_filtered(p)) where that is not NaN, else black
  *   normals   : for every pixel covered by the filtered dense map (same owner rule: the lowest-index
  *               valid covering triangle), n = sum_k w_k * vtx_normal_k / ((wa + wb) + wc) with the
@@ -493,7 +509,15 @@ static void jet_bgr(float v, float vmin, float vmax, uint8_t* bgr) {
   bgr[1] = (uint8_t)(255.0f * g + 0.5f);
   bgr[2] = (uint8_t)(255.0f * r + 0.5f);
 }
-static inline int32_t round_px(float v) { return (int32_t)(v + (v >= 0.0f ? 0.5f : -0.5f)); }
+/* Pixel of a coordinate the caller has found in reach (so |v| fits an int): half away from zero, exactly.
+ * |v| - floorf(|v|) is exact in float32; v + 0.5f is not (0.5 - 2^-25 would tie up to 1.0f). */
+static inline int32_t round_px(float v) {
+  const float a = fabsf(v), f = floorf(a);
+  const int32_t n = (int32_t)f + ((a - f) >= 0.5f ? 1 : 0);
+  return v < 0.0f ? -n : n;
+}
+/* Reach of a side's end point coordinate, R = W + H: compared in float, so a NaN is out of reach. */
+static inline int in_reach(float c, int32_t R) { return c >= -(float)R && c <= (float)(2 * R); }
 static inline void put_px(uint8_t* img, int32_t W, int32_t H, int32_t x, int32_t y, const uint8_t* c) {
   if (x < 0 || y < 0 || x >= W || y >= H) return;
   uint8_t* o = img + 3 * ((int64_t)y * W + x);
@@ -514,6 +538,9 @@ void nltgv2_debug_image(int32_t kind, int32_t W, int32_t H, float scene_color_sc
       for (int k = 0; k < 3; ++k) {
         const int32_t a = tris[3 * t + k], b = tris[3 * t + (k + 1) % 3];
         jet_bgr((0.5f * (x[a] + x[b])) * scene_color_scale, 0.0f, 2.0f, c);
+        if (!(in_reach(pos[2 * a], W + H) && in_reach(pos[2 * a + 1], W + H) && in_reach(pos[2 * b], W + H) &&
+              in_reach(pos[2 * b + 1], W + H)))
+          continue;
         int32_t x0 = round_px(pos[2 * a]), y0 = round_px(pos[2 * a + 1]);
         const int32_t x1 = round_px(pos[2 * b]), y1 = round_px(pos[2 * b + 1]);
         const int32_t dx = abs(x1 - x0), dy = -abs(y1 - y0);
@@ -531,7 +558,9 @@ void nltgv2_debug_image(int32_t kind, int32_t W, int32_t H, float scene_color_sc
   } else if (kind == 1) { /* features */
     for (int32_t f = 0; f < n_feat; ++f) {
       jet_bgr(feat_mu[f] * scene_color_scale, 0.0f, 2.0f, c);
-      const int32_t px = round_px(feat_pos[2 * f]), py = round_px(feat_pos[2 * f + 1]);
+      const float fu = feat_pos[2 * f], fv = feat_pos[2 * f + 1];
+      if (!(fu > -2.0f && fu < (float)(W + 1) && fv > -2.0f && fv < (float)(H + 1))) continue;
+      const int32_t px = round_px(fu), py = round_px(fv);
       for (int32_t dy = -1; dy <= 1; ++dy)
         for (int32_t dx = -1; dx <= 1; ++dx) put_px(bgr, W, H, px + dx, py + dy, c);
     }

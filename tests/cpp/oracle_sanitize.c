@@ -1,6 +1,8 @@
 /* tests/cpp/oracle_sanitize.c -- every oracle entry point once on a small graph, built with
- * -fsanitize=address,undefined (the reference has no sanitizer build; the oracle is the
- * checker everything else is compared with, so it gets one).  Exit code 0 = clean. */
+ * -fsanitize=address,undefined,float-cast-overflow (the reference has no sanitizer build; the
+ * oracle is the checker everything else is compared with, so it gets one; gcc's `undefined` group leaves
+ * float-cast-overflow out).  The debug images also get what no pixel holds: feature positions NaN, +-inf and
+ * +-3e9, and sides with an end out of reach.  Exit code 0 = clean. */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -70,7 +72,31 @@ int main(void) {
   float* cl = malloc(sizeof(float) * 3 * tp.width * tp.height);
   nltgv2_idepthmap(tp.width, tp.height, T, pos, x, tris, tv, 1, idm);
   nltgv2_depth_and_cloud(tp.width, tp.height, idm, Kinv, 0.1f, 100.0f, dm, cl);
-  printf("E=%d faces=%d smooth=%.6f data=%.6f scale=%.6f\n", E, nf, sm, da, scale);
-  free(edges); free(alpha); free(beta); free(q); free(row); free(inc); free(Ku); free(idm); free(dm); free(cl);
+  const float cov = nltgv2_coverage(tp.width, tp.height, idm);
+  /* the four debug images; the features sit on the vertices, then at positions no int holds: they draw nothing */
+  enum { NF = V + 8 };
+  float fpos[2 * NF], fmu[NF];
+  for (int v = 0; v < V; ++v) { fpos[2 * v] = pos[2 * v]; fpos[2 * v + 1] = pos[2 * v + 1]; fmu[v] = mu[v]; }
+  const float odd[8][2] = {{NAN, 3.0f}, {3.0f, NAN}, {INFINITY, 5.0f}, {5.0f, -INFINITY},
+                           {3e9f, 7.0f}, {7.0f, 3e9f}, {-3e9f, 9.0f}, {9.0f, -3e9f}};
+  for (int k = 0; k < 8; ++k) { fpos[2 * (V + k)] = odd[k][0]; fpos[2 * (V + k) + 1] = odd[k][1]; fmu[V + k] = k == 0 ? NAN : 0.25f * k; }
+  uint8_t* bgr = malloc((size_t)3 * tp.width * tp.height);
+  long drawn[5] = {0, 0, 0, 0, 0};
+  for (int kind = 0; kind < 4; ++kind) {
+    nltgv2_debug_image(kind, tp.width, tp.height, 0.7f, V, pos, x, T, tris, tv, vn, idm, NF, fpos, fmu, bgr);
+    for (long k = 0; k < 3L * tp.width * tp.height; ++k) drawn[kind] += bgr[k] != 0;
+  }
+  /* sides out of reach: one end beyond 2^31 px, one at NaN, one at infinity; and one that crosses the whole image */
+  const float fpos2[2 * 6] = {10.f, 10.f, 3e9f, 50.f, 100.f, NAN, -INFINITY, 20.f, -5000.f, 140.f, 5000.f, 140.f};
+  const float fx2[6] = {0.5f, 0.6f, 0.7f, 0.8f, 0.9f, 1.0f};
+  const int32_t ftris2[6] = {0, 1, 2, 3, 4, 5};
+  const uint8_t ftv2[2] = {1, 1};
+  nltgv2_debug_image(0, tp.width, tp.height, 1.0f, 6, fpos2, fx2, 2, ftris2, ftv2, NULL, NULL, 0, NULL, NULL, bgr);
+  for (long k = 0; k < 3L * tp.width * tp.height; ++k) drawn[4] += bgr[k] != 0;
+  printf("E=%d faces=%d smooth=%.6f data=%.6f scale=%.6f coverage=%.4f drawn=%ld,%ld,%ld,%ld far=%ld\n", E, nf, sm, da, scale,
+         cov, drawn[0], drawn[1], drawn[2], drawn[3], drawn[4]);
+  free(edges); free(alpha); free(beta); free(q); free(row); free(inc); free(Ku); free(idm); free(dm); free(cl); free(bgr);
+  if (!(cov > 0.0f && cov <= 1.0f && drawn[0] > 0 && drawn[1] > 0 && drawn[2] > 0 && drawn[3] > 0)) return 5;
+  if (drawn[4] != 0) return 6; /* every side of the second mesh has an end out of reach */
   return (E > 0 && isfinite(sm) && isfinite(da)) ? 0 : 4;
 }

@@ -6,6 +6,7 @@ error band; inside the band any outcome a correct float32 implementation could g
 """
 import numpy as np
 
+from oracle import debug_f64 as D
 from oracle import frame_f64 as F
 
 EPS = F.EPS32
@@ -13,6 +14,8 @@ K_IDEPTH = 8     # dense idepth: |got - f64| <= K_IDEPTH eps32 sum_k (|w_k| + m_
 K_NORMAL = 16    # normals: angle <= K_NORMAL eps32 cond (1 + 2 |P| / min |e|)
 K_POINT = 8      # mesh points, cloud: |got - f64| <= K_POINT eps32 |Kinv| |q|
 K_COST = 8       # costs: |got - f64| <= K_COST eps32 (sum of magnitudes)
+from oracle.debug_f64 import K_BLEND, K_CHAN, K_JET  # noqa: E402,F401 -- the debug images' bands: derived and stated there, where they are applied
+UNCERTAIN_CAP = 0.02  # share of an image's drawn pixels that may lie inside a band (none in a lattice or dyadic case)
 
 
 def close(got, want, tol):
@@ -161,6 +164,109 @@ def check_filter(x, edges, kind, got, what):
         sp = np.spacing(np.abs(want).astype(np.float32)).astype(np.float64)
         bad = ~close(got, want, 2 * sp + 1.01 * F.U32 * mag)
         assert not bad.any(), "%s: low-pass differs from the float64 mean: %s" % (what, _where(bad))
+
+
+# ---------------------------------------------------------------- debug images (oracle/debug_f64.py)
+def _check_image(img, got, what, exact_case, skip=None):
+    """got [H,W,3] BGR8 against a debug_f64.Image: black where nothing is drawn, byte equality where the statement is
+    certain, one of the two neighbouring levels inside the band.  Returns (drawn, uncertain) pixel counts, after
+    holding the uncertain share under its cap (none at all where exact_case)."""
+    got = np.asarray(got).reshape(-1, 3).astype(np.int64)
+    assert len(got) == len(img.drawn), what + ": image size"
+    look = np.ones(len(got), bool) if skip is None else ~skip
+    bad = look & ~img.drawn & got.any(1)
+    assert not bad.any(), "%s: drawn where the statement draws nothing: %s %s" % (what, _ids(np.flatnonzero(bad)), got[bad][:3].tolist())
+    ok = ((got >= img.lo) & (got <= img.hi)).all(1) | img.free
+    bad = look & img.drawn & ~ok
+    if bad.any():
+        p = np.flatnonzero(bad)[:4]
+        raise AssertionError("%s: %d pixels differ from the statement, first (flat index) %s: got %s want %s..%s (primitive %s)" % (
+            what, int(bad.sum()), p.tolist(), got[p].tolist(), img.lo[p].tolist(), img.hi[p].tolist(), img.key[p].tolist()))
+    drawn, unc = int((look & img.drawn).sum()), int((look & img.drawn & (img.uncertain | img.free)).sum())
+    print("%s: %d of %d drawn pixels uncertain (%.3f %%)" % (what, unc, drawn, 100.0 * unc / max(drawn, 1)))
+    if exact_case:
+        assert unc == 0, "%s: %d uncertain pixels in a case that float32 evaluates exactly" % (what, unc)
+    assert unc <= UNCERTAIN_CAP * drawn, "%s: %d of %d drawn pixels uncertain: above the cap" % (what, unc, drawn)
+    return drawn, unc
+
+
+def check_wireframe(case, x, tv, got, what, rules=D.STATED):
+    img = D.wireframe(case["W"], case["H"], case["pos"], x, case["tris"], tv, case["scale"], rules)
+    return _check_image(img, got, what + " wireframe", case["lattice"] or case["dyadic"])
+
+
+def check_features_image(case, got, what, rules=D.STATED):
+    img = D.features(case["W"], case["H"], case["feat_pos"], case["feat_mu"], case["scale"], rules)
+    return _check_image(img, got, what + " features", case["lattice"] or case["dyadic"])
+
+
+def check_idepth_image(case, idm, got, what, rules=D.STATED):
+    """idm: the implementation's own filtered dense map (pinned by check_raster): only the colouring is judged."""
+    img = D.idepth_image(idm, case["scale"], rules)
+    return _check_image(img, got, what + " idepthmap", case["lattice"] or case["dyadic"])
+
+
+def check_normals_image(case, x, tv, vn, idm, got, what, R=None, rules=D.STATED):
+    """tv, vn, idm: the implementation's own tri_valid, vertex normals and filtered dense map.  The picture is drawn
+    exactly where that map is a number; the colour is the float64 blend under the exact owner (any candidate owner
+    at an ambiguous raster pixel)."""
+    W, H = case["W"], case["H"]
+    if R is None:
+        R = F.raster(W, H, case["pos"], x, case["tris"], np.asarray(tv, bool))
+    img, (cpix, clo, chi, cfree) = D.normals(W, H, case["pos"], x, case["tris"], tv, vn, R, rules)
+    g = np.asarray(got).reshape(-1, 3).astype(np.int64)
+    covered = ~np.isnan(np.asarray(idm, np.float64).ravel())
+    bad = g.any(1) != covered
+    assert not bad.any(), "%s normals: drawn pixels are not those of the filtered map: %s" % (what, _ids(np.flatnonzero(bad)))
+    amb_ok = np.zeros(W * H, bool)
+    np.logical_or.at(amb_ok, cpix, ((g[cpix] >= clo) & (g[cpix] <= chi)).all(1) | cfree)
+    own_ok = img.drawn & (((g >= img.lo) & (g <= img.hi)).all(1) | img.free)
+    bad = R.ambiguous & covered & ~amb_ok & ~own_ok
+    assert not bad.any(), "%s normals: colour at a near-edge pixel matches no candidate owner: %s" % (what, _ids(np.flatnonzero(bad)))
+    return _check_image(img, got, what + " normals", case["lattice"] or case["dyadic"], skip=R.ambiguous)
+
+
+KINDS = ("wireframe", "features", "normals", "idepthmap")   # image kinds 0..3 (flame_hip.h FLAME_HIP_IMG_*)
+
+
+def check_debug_images(case, x, tv, vn, idm, images, what, kinds=KINDS, rules=D.STATED, R=None):
+    """The four images of one implementation (images: kind name -> [H,W,3]) with its own tri_valid, vertex normals and
+    filtered dense map (R: frame_f64.raster of that tri_valid, if the caller has it).  Returns {kind: (drawn, uncertain)}."""
+    out = {}
+    if "wireframe" in kinds:
+        out["wireframe"] = check_wireframe(case, x, tv, images["wireframe"], what, rules)
+    if "features" in kinds:
+        out["features"] = check_features_image(case, images["features"], what, rules)
+    if "normals" in kinds:
+        out["normals"] = check_normals_image(case, x, tv, vn, idm, images["normals"], what, R=R, rules=rules)
+    if "idepthmap" in kinds:
+        out["idepthmap"] = check_idepth_image(case, idm, images["idepthmap"], what, rules)
+    for k, (drawn, _) in out.items():
+        assert drawn > 0 or k not in case["draws"], "%s %s: the image is black: the case exercises nothing of this kind" % (what, k)
+    return out
+
+
+def check_read_offs(cases, images_of):
+    """What the named cases are for, read off an implementation's images directly (images_of(name) -> {kind: [H,W,3]});
+    the same read-offs for the C oracle and the device."""
+    wire = images_of("reach")["wireframe"]
+    assert not wire[12].any(), "the (-200, 12) <-> (200, 12) side is out of reach: row 12 stays black in both directions"
+    assert wire[2, :21].any(1).all() and not wire[4].any(), "x = -R is in reach, its float32 predecessor is not"
+    assert wire[6, 22:].any(1).all() and not wire[8].any(), "x = 2 R is in reach, its float32 successor is not"
+    assert wire[:2, 26].any(1).all() and not wire[:2, 28].any(), "y = -R is in reach, its float32 predecessor is not"
+    assert wire[16:, 24].any(1).all() and not wire[14:, 30].any(), "y = 2 R is in reach, its float32 successor is not"
+    wire = images_of("octants")["wireframe"]
+    assert wire[14:19, 0].any(1).all() and not wire[14:19, 1].any(), "x = 0.5 - 2^-25 is pixel 0"
+    assert wire[8:13, 0].any(1).all(), "x = -(0.5 - 2^-25) is pixel 0"
+    assert wire[0, 30:35].any(1).all() and not wire[1, 30:35].any(), "y = 0.5 - 2^-25 is pixel 0"
+    c = cases["features_edge"]
+    feat = images_of("features_edge")["features"]
+    f = int(np.flatnonzero((c["feat_pos"] == 0).all(1))[0])    # the corner feature; the NaN positions come after it
+    assert np.isnan(c["feat_pos"][f + 1:]).any()
+    lo, hi, _ = D.jet(c["feat_mu"][f:f + 1] * np.float32(c["scale"]))
+    img = D.features(c["W"], c["H"], c["feat_pos"], c["feat_mu"], c["scale"])
+    assert img.key[0] == f and feat[0, 0].tolist() == lo[0].tolist() == hi[0].tolist(), \
+        "(0, 0) belongs to the corner feature, not to a later feature at a NaN position"
 
 
 class _TP:

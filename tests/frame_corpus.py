@@ -4,7 +4,8 @@ tests/test_gpu_frame_f64.py).
 Each case is a dict: W, H, pos [V,2] f32, x [V] f32 (the vertex idepths), tris [T,3] i32, edges [E,2] (the
 unique triangle edges, i < j, plus any extra), Kinv [3,3] f32, tp (TriParams field values), min_depth /
 max_depth, lattice (every vertex on the integer grid: the float32 edge functions are exact, so the owner
-of every pixel is decided exactly), far (vertices beyond the debug images' reach: not for debug_image).
+of every pixel is decided exactly), far (vertices beyond the debug images' reach, [-(W+H), 2(W+H)] per coordinate:
+the triangle sides that end there are absent from the wireframe; tests/debug_corpus.py reads the flag).
 """
 import numpy as np
 

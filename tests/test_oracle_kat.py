@@ -284,16 +284,19 @@ def test_triangle_stage_known_answers():
 
 
 def test_oracle_is_clean_under_asan_ubsan(tmp_path):
-    """The oracle compiled with -fsanitize=address,undefined runs every entry point on a small
-    graph without a report (sanitizer build of the CPU checker)."""
+    """The oracle compiled with -fsanitize=address,undefined,float-cast-overflow runs every entry point on a small
+    graph without a report (sanitizer build of the CPU checker) -- nltgv2_coverage and the four
+    nltgv2_debug_image kinds included, with feature positions NaN, +-inf, +-3e9 and sides out of reach, which used to
+    be converted to int unchecked."""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = str(tmp_path / "oracle_sanitize")
-    subprocess.check_call(["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+    subprocess.check_call(["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined,float-cast-overflow",
+                           "-fno-sanitize-recover=all",
                            "-ffp-contract=off", "-fopenmp", os.path.join(root, "tests", "cpp", "oracle_sanitize.c"),
                            os.path.join(root, "oracle", "nltgv2_oracle.c"), "-lm", "-o", exe])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", OMP_NUM_THREADS="2")
     p = subprocess.run([exe], capture_output=True, text=True, env=env)
     assert p.returncode == 0, (p.returncode, p.stdout, p.stderr[-3000:])
-    assert p.stdout.startswith("E=")
+    assert p.stdout.startswith("E=") and " far=0" in p.stdout
