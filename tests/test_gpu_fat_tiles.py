@@ -15,13 +15,15 @@ from tests.util import assert_bit_equal, decoupled, graphgen, hooks_env, make_or
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# (vertices, expected halo depth, 12-byte slots, may a tile hold more local vertices than threads)
-FAT = [(60000, 4, 0), (100000, 3, 0), (135000, 2, 0), (160000, 1, 0), (200000, 2, 1)]
+# (vertices, expected halo depth, 12-byte slots, edges per thread): the fat resident kernels these sizes run are
+# k_tile_persist<1024, 2, 1, S12 = false, FAT = true> up to 160 k and <1024, 3, 1, S12 = true, FAT = true> at 200 k; the other
+# two fat variants -- three edges on 16-byte slots, two on 12-byte -- are tests/test_gpu_tile_cfgs.py's
+FAT = [(60000, 4, 0, 2), (100000, 3, 0, 2), (135000, 2, 0, 2), (160000, 1, 0, 2), (200000, 2, 1, 3)]
 
 
-@pytest.mark.parametrize("V,depth,slot12,dec", [pytest.param(*f, 0, id="%d-%d-%d" % f) for f in FAT] +
-                         [pytest.param(100000, 3, 0, 1, id="100000-3-0-decoupled")])
-def test_fat_resident_tiles_match_oracle(gpu, V, depth, slot12, dec):
+@pytest.mark.parametrize("V,depth,slot12,ept,dec", [pytest.param(*f, 0, id="%d-%d-%d" % f[:3]) for f in FAT] +
+                         [pytest.param(100000, 3, 0, 2, 1, id="100000-3-0-decoupled")])
+def test_fat_resident_tiles_match_oracle(gpu, V, depth, slot12, ept, dec):
     g = graphgen.synthetic(V, seed=V)
     if dec:  # beta independent of alpha, non-uniform data weights with zeros
         g = decoupled(g, V)
@@ -30,6 +32,7 @@ def test_fat_resident_tiles_match_oracle(gpu, V, depth, slot12, dec):
     o.solve(oracle_params(), iters)
     with GraphRegularizer(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, tris=g.tris, device=0) as r:
         assert r.info("num_tiles") == 256 and r.info("tile_depth") == depth and r.info("tile_slot12") == slot12
+        assert (r.info("tile_threads"), r.info("tile_ept"), r.info("tile_vpt"), r.info("tile_fat")) == (1024, ept, 1, 1)
         assert r.info("tile_lds_bytes") <= 160 * 1024
         r.step(default_params(), 40)   # (a plan's first solve: poll lists in local order, sorted local edges)
         assert r.info("persist_used") == 1 and r.last_solve_ms()[1] == 1

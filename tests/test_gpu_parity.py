@@ -367,8 +367,10 @@ def test_parameter_and_weight_variants(gpu, kw):
 def test_fuzz_sizes_and_tile_options(gpu):
     """Random graph sizes, tile sizes, halo depths, workgroup sizes and launch splits (incl. tile
     counts that are not multiples of 8 for the XCD-aware block map, tiles with very few own
-    vertices, and more tiles than the halo can separate): always the oracle's bits."""
+    vertices, and more tiles than the halo can separate): always the oracle's bits.  The kernel configurations the trials
+    reached are printed (pytest -s / -rP): the draw is no coverage of them, tests/test_gpu_tile_cfgs.py is."""
     rng = np.random.default_rng(2026)
+    reached = {}
     for trial in range(28):
         V = int(rng.integers(3, 2500))
         g = graphgen.synthetic(V, seed=100 + trial) if V >= 4 else None
@@ -390,3 +392,8 @@ def test_fuzz_sizes_and_tile_options(gpu):
             assert isinstance(e, FlameHipError) and e.code == -1 and "tile_threads" in opts, (opts, e)
             continue
         compare_state(o, r, "fuzz V=%d %s %s" % (V, opts, chunks))
+        cfg = tuple(r.info(k) for k in ("tile_threads", "tile_ept", "tile_vpt")) + ("resident" if r.info("persist_used") else "launches",)
+        reached.setdefault(cfg, []).append(trial)
+    print("fuzz: (threads, edges / thread, vertices / thread, last solve) -> trials")
+    for cfg in sorted(reached):
+        print("  %s: %s" % (cfg, reached[cfg]))
