@@ -7,7 +7,8 @@
 // renders the Detections / Matches picture of the last tracked frame (frontend_debug.hip) from the record the tracker left on the
 // device.  flame_hip_frontend_set_gates records the letterbox and the height band; every frame forms the gate record of FeFrame
 // from them and the frame's pose.  flame_hip_frontend_set_cost records the matching cost (SSD / ZSSD); every frame forms the BAD_MATCH
-// threshold of that cost and picks the tracker's instantiation.  flame_hip_frontend_set_ref_grad records the reference-patch gradient
+// threshold of that cost and picks the tracker's instantiation; flame_hip_frontend_set_gain_invariant puts the gain-invariant cost in
+// their place while it is on.  flame_hip_frontend_set_ref_grad records the reference-patch gradient
 // gate; while it is on every frame forms the epipole table behind the pose table and runs the tracker's gated instantiation.  Reads
 // no environment variable.
 #include <hip/hip_runtime.h>
@@ -74,6 +75,8 @@ struct flame_hip_frontend {
   flame_hip_frontend_gates gates = {0, 0, 0.f, 0.f, {0.f, 0.f, 0.f}};
   // matching cost (set_cost): no state depends on it, so it may change between any two frames
   int32_t cost_mode = FLAME_HIP_FE_COST_SSD;
+  // the gain-invariant cost (set_gain_invariant): while on it overrides cost_mode, which stays what set_cost set; no state either
+  int32_t gain_invariant = 0;
   // reference-patch gradient gate (set_ref_grad): 0 = off; no state depends on it either
   float min_epi_grad = 0.f;
 };
@@ -179,11 +182,12 @@ FeGates gate_record(const flame_hip_frontend* fe, const double* T) {
 }
 
 // The BAD_MATCH threshold of a frame (DESIGN.md 5.3 "Matching cost"): bad = max_match_error win^2 65536 bounds the SSD cost; the
-// ZSSD cost n S2 - S1^2 is bounded by n bad, saturated at UINT64_MAX (tests/fe_zm_ref.py bad_threshold() is the same statement).
-uint64_t bad_threshold(float max_match_error, int32_t win, int32_t cost_mode) {
+// ZSSD cost n S2 - S1^2 is bounded by n bad, saturated at UINT64_MAX (tests/fe_zm_ref.py bad_threshold() is the same statement), and
+// so is the gain-invariant cost, whose unit is the same.  `cost` is the tracker's selector (kFeCost*).
+uint64_t bad_threshold(float max_match_error, int32_t win, int cost) {
   const uint64_t n = (uint64_t)(win * win);
   const uint64_t bad = (uint64_t)((double)max_match_error * (double)(win * win) * 65536.0);
-  if (cost_mode != FLAME_HIP_FE_COST_ZSSD) return bad;
+  if (cost == kFeCostSsd) return bad;
   return bad > UINT64_MAX / n ? UINT64_MAX : n * bad;
 }
 
@@ -317,8 +321,8 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
   f.idepth_min = params->idepth_min; f.idepth_max = params->idepth_max;
   f.idepth_init = params->idepth_init; f.var_init = params->var_init;
   f.epipolar_line_var = params->epipolar_line_var;
-  const bool zero_mean = fe->cost_mode == FLAME_HIP_FE_COST_ZSSD;
-  f.bad_match_cost = bad_threshold(params->max_match_error, f.win, fe->cost_mode);
+  const int cost = fe->gain_invariant ? kFeCostGi : fe->cost_mode == FLAME_HIP_FE_COST_ZSSD ? kFeCostZssd : kFeCostSsd;
+  f.bad_match_cost = bad_threshold(params->max_match_error, f.win, cost);
   const bool ref_grad = fe->min_epi_grad > 0.f;
   f.min_epi_grad = fe->min_epi_grad;
   f.is_poseframe = is_poseframe ? 1 : 0;
@@ -371,7 +375,7 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
   FE_HIP(hipMemsetAsync(fe->d_cell_key, 0xFF, (sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)ncells, s));
   FE_HIP(hipMemsetAsync(fe->d_counts, 0, sizeof(int32_t) * kFeCounts, s));
   if (overwrote) fe_launch_kill(s, f, valid_mask(fe));
-  fe_launch_track(s, f, zero_mean, ref_grad);
+  fe_launch_track(s, f, cost, ref_grad);
   if (is_poseframe) fe_launch_detect(s, f);
   fe_launch_compact(s, f);
   FE_HIP(hipGetLastError());
@@ -474,6 +478,12 @@ int flame_hip_frontend_set_gates(flame_hip_frontend* fe, const flame_hip_fronten
 int flame_hip_frontend_set_cost(flame_hip_frontend* fe, int32_t mode) {
   if (!fe || (mode != FLAME_HIP_FE_COST_SSD && mode != FLAME_HIP_FE_COST_ZSSD)) return FLAME_HIP_ERR_ARG;
   fe->cost_mode = mode;  // takes effect with the next frame
+  return 0;
+}
+
+int flame_hip_frontend_set_gain_invariant(flame_hip_frontend* fe, int32_t on) {
+  if (!fe || (on != 0 && on != 1)) return FLAME_HIP_ERR_ARG;
+  fe->gain_invariant = on;  // takes effect with the next frame; cost_mode stays what set_cost set
   return 0;
 }
 
@@ -640,6 +650,7 @@ int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* va
   if (!std::strcmp(key, "debug_image_device_us")) { *value = (int64_t)(fe->debug_image_device_us + 0.5); return 0; }
   if (!std::strcmp(key, "gates")) { *value = (fe->gates.letterbox ? 1 : 0) | (fe->gates.height_gate ? 2 : 0); return 0; }
   if (!std::strcmp(key, "cost_mode")) { *value = fe->cost_mode; return 0; }
+  if (!std::strcmp(key, "gain_invariant")) { *value = fe->gain_invariant; return 0; }
   if (!std::strcmp(key, "ref_grad")) { *value = fe->min_epi_grad > 0.f ? 1 : 0; return 0; }
   if (!std::strcmp(key, "fail_ref_grad")) { *value = fe->counts[12]; return 0; }
   if (!std::strcmp(key, "held_height")) { *value = fe->counts[10]; return 0; }

@@ -117,8 +117,9 @@ struct FeFrame {
 };
 
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask);
-// zero_mean: the ZSSD cost (f.bad_match_cost is that cost's threshold); ref_grad: the reference-patch gradient gate (f.min_epi_grad, f.epi)
-void fe_launch_track(hipStream_t s, const FeFrame& f, bool zero_mean, bool ref_grad);
+// cost: the matching cost of the frame (f.bad_match_cost is that cost's threshold); ref_grad: the reference-patch gradient gate (f.min_epi_grad, f.epi)
+enum { kFeCostSsd = 0, kFeCostZssd = 1, kFeCostGi = 2 };
+void fe_launch_track(hipStream_t s, const FeFrame& f, int cost, bool ref_grad);
 void fe_launch_detect(hipStream_t s, const FeFrame& f);
 void fe_launch_compact(hipStream_t s, const FeFrame& f);
 

@@ -76,6 +76,77 @@ __device__ __forceinline__ unsigned long long fe_cost(const FeFrame& f, const ui
   return C;
 }
 
+// The gain-invariant cost (DESIGN.md 5.3 "Matching cost", flame_hip_frontend_set_gain_invariant): the residual of the reference
+// window after the best fit ref ~ g cur + b.  With I_i the bilinear sum of the current image (0 ... 65 280) and R_i = 256 ref_i
+// over the n = win^2 window pixels, SI = sum I (< 2^23), SII = sum I^2, SIR = sum I R (each term < 2^32, the sums < 2^39) and
+//   ZI = n SII - SI^2 (>= 0, < 2^45),  ZIR = n SIR - SI SR (signed, |ZIR| < 2^45),  ZR = n SRR - SR^2 (>= 0, < 2^45)
+// are exact integers; ZI == 0 (a flat current window) or ZIR <= 0 (anti-correlation is refused) leaves C = ZR, otherwise
+//   C = floor(ZR - ZIR^2 / ZI), clamped at 0:
+// a double multiply, divide and subtract on integers below 2^53, each rounded once (-ffp-contract=off) -- the bits of NumPy's
+// float64.  C <= ZR < 2^45: the argmin key keeps its width.  The unit is ZSSD's (n^2 x a variance in 256-scaled grey levels).
+// fe_ref_sums forms (SR, ZR) of the feature once, before the search: the 64 lanes cover the n <= 81 reference pixels in two
+// passes, s1 = sum ref <= 81 * 255 and s2 = sum ref^2 <= 81 * 255^2 < 2^23 are int32 sums an xor butterfly leaves in every lane
+// (any order: the same integers), SR = 256 s1 and ZR = 65536 (n s2 - s1^2).  The caller has tested that the window lies inside.
+__device__ __forceinline__ void fe_ref_sums(const FeFrame& f, const uint8_t* __restrict__ ref, int u, int v, int lane, unsigned int* SR,
+                                            unsigned long long* ZR) {
+  const int r = f.win >> 1, n = f.win * f.win;
+  int s1 = 0, s2 = 0;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int i = lane + 64 * pass;
+    if (i < n) {
+      const int q = ref[(size_t)(v - r + i / f.win) * f.W + (u - r + i % f.win)];
+      s1 += q;
+      s2 += q * q;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s1 += __shfl_xor(s1, o, 64);
+    s2 += __shfl_xor(s2, o, 64);
+  }
+  const unsigned int t1 = (unsigned int)__builtin_amdgcn_readfirstlane(s1), t2 = (unsigned int)__builtin_amdgcn_readfirstlane(s2);
+  *SR = 256u * t1;  // (wave-uniform: both live in scalar registers through the search)
+  *ZR = (unsigned long long)((unsigned int)n * t2 - t1 * t1) << 16;
+}
+
+__device__ __forceinline__ unsigned long long fe_cost_gi(const FeFrame& f, const uint8_t* __restrict__ ref, int u, int v, float px,
+                                                         float py, unsigned int SR, unsigned long long ZR) {
+  const float fqx = floorf(px * 16.0f + 0.5f), fqy = floorf(py * 16.0f + 0.5f);
+  if (!(fqx >= 0.0f && fqx <= (float)(16 * f.W) && fqy >= 0.0f && fqy <= (float)(16 * f.H))) return kNone;
+  const int qx = (int)fqx, qy = (int)fqy;
+  const int ix = qx >> 4, iy = qy >> 4;
+  const int r = f.win >> 1;
+  if (ix - r < 0 || iy - r < 0 || ix + r + 1 > f.W - 1 || iy + r + 1 > f.H - 1) return kNone;
+  const int wx1 = qx & 15, wx0 = 16 - wx1, wy1 = qy & 15, wy0 = 16 - wy1;
+  unsigned long long SII = 0, SIR = 0;
+  unsigned int SI = 0;
+  for (int dy = -r; dy <= r; ++dy) {
+    const uint8_t* __restrict__ r0 = f.cur + (size_t)(iy + dy) * f.W + (ix - r);
+    const uint8_t* __restrict__ r1 = r0 + f.W;
+    const uint8_t* __restrict__ rr = ref + (size_t)(v + dy) * f.W + (u - r);
+    int t0 = r0[0], b0 = r1[0];
+    for (int dx = 0; dx < f.win; ++dx) {
+      const int t1 = r0[dx + 1], b1 = r1[dx + 1];
+      const unsigned int I = (unsigned int)(wy0 * (wx0 * t0 + wx1 * t1) + wy1 * (wx0 * b0 + wx1 * b1));  // <= 65 280
+      const unsigned int R = 256u * (unsigned int)rr[dx];                                                   // <= 65 280
+      SI += I;
+      SII += (unsigned long long)(I * I);  // (both products fit 32 bits)
+      SIR += (unsigned long long)(I * R);
+      t0 = t1;
+      b0 = b1;
+    }
+  }
+  const unsigned long long n = (unsigned long long)(unsigned int)(f.win * f.win);
+  const unsigned long long ZI = n * SII - (unsigned long long)SI * (unsigned long long)SI;
+  const long long ZIR = (long long)(n * SIR) - (long long)((unsigned long long)SI * (unsigned long long)SR);
+  if (ZI == 0ull || ZIR <= 0ll) return ZR;
+  const double z = (double)ZIR;
+  const double q = (z * z) / (double)ZI;
+  const double Cd = (double)ZR - q;
+  return Cd > 0.0 ? (unsigned long long)floor(Cd) : 0ull;
+}
+
 // The reference-patch gradient gate (DESIGN.md 5.3 "Reference-patch gradient"): does the win x win reference window have structure
 // ALONG the epipolar line?  The 64 lanes cover the n <= 81 window pixels in two passes; the three sums of the structure tensor are
 // integers (each <= 81 * 255^2 < 2^24: exact as float32) and an xor butterfly leaves them in every lane, so the result is
@@ -117,10 +188,11 @@ __global__ __launch_bounds__(256) void k_fe_kill(FeFrame f, unsigned long long v
   if (f.alive[slot] && !((valid_mask >> f.pf[slot]) & 1ull)) f.alive[slot] = 0;
 }
 
-// ZM picks the matching cost (false: SSD, true: ZSSD); f.bad_match_cost is the host's threshold for that cost.  Everything
-// behind the cost -- argmin, BAD_MATCH, AMBIGUOUS, the parabola -- takes it as it comes.  RG puts the reference-patch gradient
-// gate between the NO_PARALLAX test and the search; the instantiations without it hold none of its code.
-template <bool ZM, bool RG>
+// COST picks the matching cost (kFeCostSsd, kFeCostZssd, kFeCostGi: the gain-invariant one); f.bad_match_cost is the host's
+// threshold for that cost.  Everything behind the cost -- argmin, BAD_MATCH, AMBIGUOUS, the parabola -- takes it as it comes; the
+// gain-invariant cost adds one decision, BAD_MATCH for a flat reference window (ZR == 0: nothing to correlate).  RG puts the
+// reference-patch gradient gate between the NO_PARALLAX test and the search; the instantiations without it hold none of its code.
+template <int COST, bool RG>
 __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
   const int lane = threadIdx.x & 63;
   const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -177,13 +249,19 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
       steps = S;
       unsigned long long C[kFePasses];
       unsigned long long best = kNone;
+      unsigned int SR = 0u;
+      unsigned long long ZR = 0ull;
+      if (COST == kFeCostGi) fe_ref_sums(f, ref, u, v, lane, &SR, &ZR);
 #pragma unroll
       for (int pass = 0; pass < kFePasses; ++pass) {
         const int k = lane + 64 * pass;
         unsigned long long c = kNone;
-        if (64 * pass <= S && k <= S) c = fe_cost<ZM>(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey);
+        if (64 * pass <= S && k <= S) {
+          if constexpr (COST == kFeCostGi) c = fe_cost_gi(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey, SR, ZR);
+          else c = fe_cost<COST == kFeCostZssd>(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey);
+        }
         C[pass] = c;
-        if (c != kNone) {  // (c < 2^39 -- ZM: c < 2^45 --, k < 2^9: one 64-bit key < 2^54 orders by cost, then by k)
+        if (c != kNone) {  // (c < 2^39 -- ZSSD, GI: c < 2^45 --, k < 2^9: one 64-bit key < 2^54 orders by cost, then by k)
           const unsigned long long key = (c << 9) | (unsigned long long)k;
           best = key < best ? key : best;
         }
@@ -194,7 +272,7 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
       } else {
         ks = (int)(best & 511ull);
         const unsigned long long Cbest = best >> 9;
-        if (Cbest > f.bad_match_cost) {
+        if ((COST == kFeCostGi && ZR == 0ull) || Cbest > f.bad_match_cost) {
           status = kFeBadMatch;
         } else {
           bool amb = false;
@@ -454,14 +532,16 @@ __global__ __launch_bounds__(1024) void k_fe_compact(FeFrame f) {
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask) {
   hipLaunchKernelGGL(k_fe_kill, dim3((f.max_features + 255) / 256), dim3(256), 0, s, f, valid_mask);
 }
-void fe_launch_track(hipStream_t s, const FeFrame& f, bool zero_mean, bool ref_grad) {
+void fe_launch_track(hipStream_t s, const FeFrame& f, int cost, bool ref_grad) {
   const dim3 grid((f.max_features + 3) / 4), block(256);
   if (ref_grad) {
-    if (zero_mean) hipLaunchKernelGGL((k_fe_track<true, true>), grid, block, 0, s, f);
-    else hipLaunchKernelGGL((k_fe_track<false, true>), grid, block, 0, s, f);
+    if (cost == kFeCostGi) hipLaunchKernelGGL((k_fe_track<kFeCostGi, true>), grid, block, 0, s, f);
+    else if (cost == kFeCostZssd) hipLaunchKernelGGL((k_fe_track<kFeCostZssd, true>), grid, block, 0, s, f);
+    else hipLaunchKernelGGL((k_fe_track<kFeCostSsd, true>), grid, block, 0, s, f);
   } else {
-    if (zero_mean) hipLaunchKernelGGL((k_fe_track<true, false>), grid, block, 0, s, f);
-    else hipLaunchKernelGGL((k_fe_track<false, false>), grid, block, 0, s, f);
+    if (cost == kFeCostGi) hipLaunchKernelGGL((k_fe_track<kFeCostGi, false>), grid, block, 0, s, f);
+    else if (cost == kFeCostZssd) hipLaunchKernelGGL((k_fe_track<kFeCostZssd, false>), grid, block, 0, s, f);
+    else hipLaunchKernelGGL((k_fe_track<kFeCostSsd, false>), grid, block, 0, s, f);
   }
 }
 void fe_launch_detect(hipStream_t s, const FeFrame& f) {

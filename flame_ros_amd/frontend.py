@@ -132,6 +132,13 @@ class GpuFrontEnd:
         (the default).  May change between any two frames."""
         _l.check(self._lib.flame_hip_frontend_set_cost(self._h, COST_ZSSD if zero_mean else COST_SSD), "flame_hip_frontend_set_cost")
 
+    def set_gain_invariant(self, on=True):
+        """The gain-invariant matching cost for the frames to come: the residual of the reference window after the best fit
+        ref ~ g cur + b -- bit-invariant to a power-of-two gain and any offset on the frames tracked against a pose frame that clip
+        nowhere; an exposure step (a gain) is what it is for.  While on it overrides `set_cost`; `on=False` returns to that
+        choice.  May change between any two frames."""
+        _l.check(self._lib.flame_hip_frontend_set_gain_invariant(self._h, 1 if on else 0), "flame_hip_frontend_set_gain_invariant")
+
     def set_ref_grad(self, min_grad):
         """The reference-patch gradient gate of the frames to come: a feature whose reference window has a root-mean-square grey
         gradient below `min_grad` ALONG its epipolar line (an edge parallel to the line: the aperture problem) is not searched and

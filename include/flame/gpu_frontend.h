@@ -31,7 +31,9 @@
 // MATCHING COST (flame_hip.h, flame_hip_frontend_set_cost; DESIGN.md 5.3 "Matching cost"): the constructor honours
 // Params::zero_mean_matching (this build's own switch: the zero-mean SSD, bit-invariant to a grey offset between the pose frame
 // and the current image); setZeroMean() changes it later, between any two frames.  With the switch off no call is made at all.  A
-// refusal lands in lastError() and fails every track() until a call succeeds, as with the gates.
+// refusal lands in lastError() and fails every track() until a call succeeds, as with the gates.  ZSSD does not remove a gain;
+// Params::gain_invariant_matching (flame_hip_frontend_set_gain_invariant) does: the constructor honours it the same way -- off: no
+// call at all --, setGainInvariant() changes it later, and while it is on it overrides the SSD / ZSSD choice.
 //
 // REFERENCE-PATCH GRADIENT (flame_hip.h, flame_hip_frontend_set_ref_grad; DESIGN.md 5.3 "Reference-patch gradient"): the constructor
 // honours Params::min_epipolar_grad (this build's own switch: a feature whose reference window has no structure along its epipolar
@@ -75,6 +77,11 @@ class GpuFrontEnd {
     if (handle_ && params.zero_mean_matching) {  // (off: no call at all)
       setZeroMean(true);
       if (gates_error_) last_error_ = gates_error_;  // (a refused gate record stays what lastError() shows)
+    }
+    if (handle_ && params.gain_invariant_matching) {  // (off: no call at all)
+      const int before = last_error_;
+      setGainInvariant(true);
+      if (before) last_error_ = before;  // (an earlier refusal stays what lastError() shows)
     }
     if (handle_ && params.min_epipolar_grad != 0.f) {  // (off: no call at all)
       const int before = last_error_;
@@ -145,6 +152,18 @@ class GpuFrontEnd {
   }
   bool zeroMean() const { return zero_mean_; }
 
+  // The gain-invariant matching cost of the frames to come (true), which overrides the SSD / ZSSD choice while it is on, or that
+  // choice again (false, the default).  May change between any two frames.  false (lastError()) when the library refuses; track()
+  // then fails until a call succeeds.
+  bool setGainInvariant(bool on) {
+    if (!handle_) return false;
+    gain_invariant_error_ = flame_hip_frontend_set_gain_invariant(handle_, on ? 1 : 0);
+    last_error_ = gain_invariant_error_;
+    if (!gain_invariant_error_) gain_invariant_ = on;
+    return gain_invariant_error_ == 0;
+  }
+  bool gainInvariant() const { return gain_invariant_; }
+
   // The reference-patch gradient gate of the frames to come: the smallest root-mean-square grey gradient along the epipolar line a
   // reference window needs to be searched; 0 = off (the default).  May change between any two frames.  false (lastError()) when
   // the library refuses the value (negative, non-finite): the gate stays what it was and track() fails until a call succeeds.
@@ -200,6 +219,7 @@ class GpuFrontEnd {
     if (!handle_) return false;  // (lastError() still holds why the handle could not be made)
     if (gates_error_) return fail(gates_error_);  // (a refused gate record is not tracked around)
     if (cost_error_) return fail(cost_error_);    // (nor a refused matching cost)
+    if (gain_invariant_error_) return fail(gain_invariant_error_);
     if (ref_grad_error_) return fail(ref_grad_error_);  // (nor a refused gradient gate)
     rectified_valid_ = false;
     const int rows = have_camera_ ? raw_height_ : height_, cols = have_camera_ ? raw_width_ : width_;
@@ -285,6 +305,8 @@ class GpuFrontEnd {
   int gates_error_ = 0;  // what the library said to the last gate record
   bool zero_mean_ = false;
   int cost_error_ = 0;   // ... and to the last matching cost
+  bool gain_invariant_ = false;
+  int gain_invariant_error_ = 0;  // ... and to the last gain-invariant switch
   float min_epipolar_grad_ = 0.f;
   int ref_grad_error_ = 0;  // ... and to the last gradient gate
   flame_hip_frontend* handle_ = nullptr;

@@ -73,9 +73,16 @@ struct Params {
   // (this build's own) the matching cost of flame::GpuFrontEnd's epipolar search (gpu_frontend.h; DESIGN.md 5.3 "Matching cost"):
   // true = zero-mean SSD (flame_hip_frontend_set_cost, FLAME_HIP_FE_COST_ZSSD), which a grey offset between a pose frame and the
   // images tracked against it cannot move -- for cameras with auto-exposure (TUM's Kinect, EuRoC); use zparams.win_size >= 7 with
-  // it.  Gain is not removed.  Off by default: with it off the front end makes exactly the calls it made before.  Any other
+  // it.  Gain is not removed by this cost; gain_invariant_matching below removes it.  Off by default: with it off the front end makes exactly the calls it made before.  Any other
   // registered FrontEnd gets the field carried and has to honour it itself.
   bool zero_mean_matching = false;
+  // (this build's own) true = the gain-invariant matching cost (flame_hip_frontend_set_gain_invariant; DESIGN.md 5.3 "Matching
+  // cost"): the residual of the reference window after the best fit ref ~ g cur + b, which neither a gain (an exposure step) nor
+  // an offset on the images tracked against a pose frame moves -- bit for bit for a power-of-two gain that clips nowhere, up to
+  // the 8-bit rounding of the image otherwise.  While on it overrides zero_mean_matching.  A gain on the pose frame itself is not
+  // removed.  Off by default: with it off the front end makes exactly the calls it made before.  Any other registered FrontEnd
+  // gets the field carried and has to honour it itself.
+  bool gain_invariant_matching = false;
   // (this build's own) the reference-patch gradient gate of flame::GpuFrontEnd's tracker (gpu_frontend.h; DESIGN.md 5.3
   // "Reference-patch gradient"; flame_hip_frontend_set_ref_grad): a feature whose reference window has a root-mean-square grey
   // gradient below this ALONG its epipolar line -- an edge parallel to the line, the aperture problem -- is not searched in that

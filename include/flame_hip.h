@@ -513,7 +513,7 @@ typedef struct {
   float idepth_min, idepth_max; /* search interval clamp (0.01, 10) */
   float idepth_init, var_init;  /* prior of a new feature (0.5, 0.25) */
   float max_match_error;        /* grey^2 per window pixel above which the best match is rejected (100); with the ZSSD cost
-                                 * (flame_hip_frontend_set_cost) it bounds the residual's variance per pixel, not its mean square */
+                                 * (flame_hip_frontend_set_cost) and the gain-invariant one (_set_gain_invariant) it bounds the residual's variance per pixel, not its mean square */
 } flame_hip_frontend_params;
 /* status of a feature in its last frame; the first four failures are in the order they are tested */
 enum {
@@ -557,7 +557,7 @@ int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* 
  * around the raw upload and the ingest stage of the last _track_raw / _rectify; 0 after a _track), "ingest_raw_bytes" (what that
  * call uploaded); "gates" (bit 0 = letterbox, bit 1 = height band: what _set_gates last set), "held_height" / "refused_letterbox"
  * (features of the last frame the height band held / whose projection the letterbox refused); "cost_mode" (FLAME_HIP_FE_COST_*:
- * what _set_cost last set); "ref_grad" (1 while the gate of _set_ref_grad is on), "fail_ref_grad" (features of the last frame with
+ * what _set_cost last set); "gain_invariant" (what _set_gain_invariant last set); "ref_grad" (1 while the gate of _set_ref_grad is on), "fail_ref_grad" (features of the last frame with
  * status REF_GRAD) */
 int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value);
 /* Debug/test hook: every slot's state (max_features entries each; any pointer may be NULL): alive, reference pixel (u, v),
@@ -654,12 +654,33 @@ int flame_hip_frontend_set_gates(flame_hip_frontend* fe, const flame_hip_fronten
  * with bad = (uint64)(max_match_error win_size^2 65536).  C replaces the SSD cost in every decision -- validity, argmin (ties to
  * the smallest sample), BAD_MATCH, AMBIGUOUS, the sub-sample parabola -- and nothing else changes.  A grey offset between the
  * pose frame and the current image that clips nowhere adds 256 b to every D_i and leaves the ZSSD cost the same integer: the
- * whole tracker is bit-invariant to it (auto-exposure cameras).  A GAIN is not removed.  On very smooth imagery a small window
+ * whole tracker is bit-invariant to it (auto-exposure cameras).  A GAIN is not removed by ZSSD: a change of the exposure TIME is
+ * one, and flame_hip_frontend_set_gain_invariant below removes it.  On very smooth imagery a small window
  * cannot tell a shift along a ramp from an offset: use win_size >= 7 with ZSSD.
  * Takes effect with the next _track / _track_raw and may change in mid-sequence (the feature state holds no cost).  Valid on a
  * handle without a device.  Errors: ARG (NULL fe, unknown mode). */
 enum { FLAME_HIP_FE_COST_SSD = 0, FLAME_HIP_FE_COST_ZSSD = 1 };
 int flame_hip_frontend_set_cost(flame_hip_frontend* fe, int32_t mode);
+
+/* ---- gain-invariant matching cost (opt-in): auto-exposure changes the exposure time, and that is a gain.  ZSSD under a gain of
+ * 0.8 has four times the median inverse-depth error and under 0.6 loses nearly every search.  With on = 1 the tracker
+ * matches with the residual of the reference window after the best fit ref ~ g cur + b, anti-correlation refused (DESIGN.md 5.3
+ * "Matching cost"; restated in tests/fe_gi_ref.py, which the GPU equals bit for bit).  Over the n = win_size^2 window pixels, with
+ * I_i = sum of the bilinear weights x current pixels (0 ... 65 280) and R_i = 256 x reference pixel, in exact integers:
+ *   ZI = n sum I^2 - (sum I)^2,  ZR = n sum R^2 - (sum R)^2,  ZIR = n sum I R - (sum I)(sum R)   (each below 2^45 in magnitude);
+ *   C = ZR                                   when ZI == 0 or ZIR <= 0,
+ *   C = max(0, floor(ZR - ZIR^2 / ZI))       otherwise: a double multiply, divide and subtract, each rounded once (IEEE).
+ * C replaces the cost in every decision exactly as ZSSD's does; BAD_MATCH when C > n bad (ZSSD's threshold: the unit is the same),
+ * and, tested before the threshold, when ZR == 0 (a flat reference window has nothing to correlate).  Nothing else changes.
+ * A tracked frame I' = 2^m I + b that clips nowhere, against an unchanged pose frame, scales ZI by 4^m and ZIR by 2^m exactly, and
+ * a power of two commutes with IEEE rounding: C keeps its bits, and so does everything the tracker puts out.  An offset on a pose
+ * frame leaves ZR and ZIR the same integers.  A general gain is invariant up to the rounding of the 8-bit image (measured in
+ * DESIGN.md 6).  A GAIN ON A POSE FRAME scales C and moves the detector: it is not claimed invariant.
+ * While on it overrides the SSD / ZSSD choice of _set_cost; info key "cost_mode" keeps reporting what _set_cost set, info key
+ * "gain_invariant" this switch.  Takes effect with the next _track / _track_raw and may change in mid-sequence (the feature state
+ * holds no cost).  Valid on a handle without a device.  Errors: ARG (NULL fe, on outside {0, 1}); the setting then stays what it
+ * was. */
+int flame_hip_frontend_set_gain_invariant(flame_hip_frontend* fe, int32_t on);
 
 /* ---- reference-patch gradient gate (opt-in): an edge parallel to the epipolar line slides along itself, every sample of the search
  * costs about the same and the minimum that gets fused is noise (the aperture problem).  With min_grad > 0 the tracker asks, after

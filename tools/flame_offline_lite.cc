@@ -41,6 +41,9 @@
 // (flame_hip_frontend_set_cost), which a grey offset between a pose frame and the frames tracked against it cannot move: for
 // sequences from auto-exposure cameras.  The frame line ends with `cost_mode 1`.  --win-size N (needs --gpu-frontend):
 // Params::zparams.win_size, the matching window (odd, <= 9; the zero-mean cost wants >= 7 on smooth imagery).
+// --gain-invariant (needs --gpu-frontend): Params::gain_invariant_matching -- the tracker matches with the gain-invariant cost
+// (flame_hip_frontend_set_gain_invariant), which neither an exposure step (a gain) nor an offset on the frames tracked against a
+// pose frame moves; it overrides --zero-mean.  The frame line ends with `gain_invariant 1`.
 // --min-epipolar-grad G (needs --gpu-frontend): Params::min_epipolar_grad -- the tracker's reference-patch gradient gate
 // (flame_hip_frontend_set_ref_grad): a feature whose reference window has a root-mean-square gradient below G along its epipolar
 // line is not searched.  The frame line ends with `fail_ref_grad <n>`, the stat key num_fail_ref_patch_grad of the frame.
@@ -209,6 +212,11 @@ struct Lite {
     }
     if (params.min_epipolar_grad != 0.f)  // (appended at the end: without the flag the line is what it was)
       std::printf(" fail_ref_grad %d", st.stats().count("num_fail_ref_patch_grad") ? static_cast<int>(st.stats("num_fail_ref_patch_grad")) : -1);
+    if (params.gain_invariant_matching) {  // (appended at the end: without the flag the line is what it was)
+      int64_t on = -1;
+      if (gpu && gpu->handle()) flame_hip_frontend_info(gpu->handle(), "gain_invariant", &on);
+      std::printf(" gain_invariant %d", static_cast<int>(on));
+    }
     std::printf("\n");
   }
 };
@@ -227,6 +235,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[k], "--gpu-frontend")) L.gpu_frontend = true;           // features from flame::GpuFrontEnd
     else if (!std::strcmp(argv[k], "--debug-images") && k + 1 < argc) L.debug_dir = argv[++k];
     else if (!std::strcmp(argv[k], "--zero-mean")) L.params.zero_mean_matching = true;
+    else if (!std::strcmp(argv[k], "--gain-invariant")) L.params.gain_invariant_matching = true;
     else if (!std::strcmp(argv[k], "--win-size") && k + 1 < argc) { L.params.zparams.win_size = std::atoi(argv[++k]); win_flag = true; }
     else if (!std::strcmp(argv[k], "--min-epipolar-grad") && k + 1 < argc) { L.params.min_epipolar_grad = static_cast<float>(std::atof(argv[++k])); rg_flag = true; }
     else if (!std::strcmp(argv[k], "--letterbox")) { L.params.do_letterbox = true; L.gates = true; }
@@ -241,12 +250,13 @@ int main(int argc, char** argv) {
   const bool asl = !args.empty() && !std::strcmp(args[0], "asl");
   if (!args.empty() && (!std::strcmp(args[0], "tum") || asl)) args.erase(args.begin());
   const bool bad_flags = (!L.debug_dir.empty() && !L.gpu_frontend) || (!L.dump_dir.empty() && L.gpu_frontend) ||
-                         ((L.gates || L.have_up || L.params.zero_mean_matching || win_flag || rg_flag) && !L.gpu_frontend) || bad_up;
+                         ((L.gates || L.have_up || L.params.zero_mean_matching || L.params.gain_invariant_matching || win_flag || rg_flag) && !L.gpu_frontend) || bad_up;
   if (bad_flags || (asl && args.size() < 4) || (!asl && args.size() < 6)) {
     std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-frontend [--debug-images dir]]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-rectify] [--gpu-frontend [--debug-images dir]]\n"
                  "  --gpu-frontend: features from the GPU tracker (not with --dump); --debug-images dir: detections_<id>.ppm / matches_<id>.ppm per frame (needs --gpu-frontend)\n"
                  "  --letterbox, --min-height H, --max-height H, --up-axis x,y,z (need --gpu-frontend): features only in the middle third of the rows / only inside the height band along the up axis (default 0,-1,0)\n"
                  "  --zero-mean (needs --gpu-frontend): match with the zero-mean SSD, which a grey offset between frames cannot move (auto-exposure cameras); --win-size N: the matching window (odd, <= 9)\n"
+                 "  --gain-invariant (needs --gpu-frontend): match with the gain-invariant cost, which an exposure step between frames cannot move; overrides --zero-mean\n"
                  "  --min-epipolar-grad G (needs --gpu-frontend): do not search a feature whose reference window has a gradient below G along its epipolar line (0 = off)\n",
                  argv[0], argv[0]);
     return 2;
