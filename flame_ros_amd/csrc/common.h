@@ -112,6 +112,48 @@ FLAME_HD inline uint32_t morton_spread16(uint32_t x) {
   return x;
 }
 
+// ---- per-element rules of the graph sync and the plan: ONE statement each for the host builder (plan.cpp, sync.cpp), the
+// staged device kernels and the one-launch plan (plan_dev.hip); DESIGN.md lists who calls what.  They take values, not
+// arrays: the callers keep their operands in registers, LDS or vectors as suits them. ----
+// Morton code of a position inside the box [mn, mx]: quantise to 16 bits per axis, spread.  The clamp is the identity for a box
+// that is the frame's own (the host builder, a bisected device plan); a reused partition keeps the box of the frame it was made from.
+FLAME_HD inline uint32_t morton_quant16(float x, float mn, float mx) { return (uint32_t)(65535.0f * (fminf(fmaxf(x, mn), mx) - mn) / fmaxf(mx - mn, 1e-20f)); }
+FLAME_HD inline uint32_t morton_code(float x, float y, float mnx, float mny, float mxx, float mxy) {
+  return morton_spread16(morton_quant16(x, mnx, mxx)) | (morton_spread16(morton_quant16(y, mny, mxy)) << 1);
+}
+// ... and the sort key of vertex v inside its tile: (code, id)
+FLAME_HD inline uint64_t morton_key(uint32_t code, int32_t v) { return ((uint64_t)code << 32) | (uint32_t)v; }
+// Side (u, w) of a triangle as the half edge (min, max); false: an index out of range or a degenerate side
+FLAME_HD inline bool tri_side(int32_t u, int32_t w, int32_t V, int32_t* lo, int32_t* hi) {
+  *lo = u < w ? u : w; *hi = u < w ? w : u;
+  return !(u < 0 || w < 0 || u >= V || w >= V || u == w);
+}
+// Edge weight of the graph sync: 1 / length, dx * dx + dy * dy in two roundings (-ffp-contract=off), as the oracle states it
+FLAME_HD inline float edge_alpha(float dx, float dy) { return 1.0f / sqrtf(dx * dx + dy * dy); }
+// Data terms of the graph sync; pred: the prediction, or any non-finite value where there is none (or it is not used)
+struct DataTerm { float z, wgt, x0; };
+FLAME_HD inline DataTerm data_term(float mu, float var, float pred, float scale, bool adaptive) {
+  DataTerm d;
+  d.z = mu / scale;
+  d.wgt = adaptive ? 1.0f / var : 1.0f;
+  d.x0 = isfinite(pred) ? pred / scale : d.z;
+  return d;
+}
+FLAME_HD inline bool data_term_finite(const DataTerm& d) { return isfinite(d.z) && isfinite(d.wgt) && isfinite(d.x0); }
+// Edge record {alpha, beta, d}: d = d_sign * (pos_i - pos_j) (a multiplication by +-1 is exact)
+FLAME_HD inline float edge_dsign(int d_sign) { return d_sign < 0 ? -1.0f : 1.0f; }
+template <class F4>
+FLAME_HD inline F4 edge_record(float alpha, float beta, float dsign, float xi, float yi, float xj, float yj) {
+  return F4{alpha, beta, dsign * (xi - xj), dsign * (yi - yj)};
+}
+// Incidence entry of a vertex's row: while the row is sorted, (ORIGINAL edge id << 1 | role) -- ascending entry = ascending
+// original id, the summation order of the arithmetic contract; role 1: the vertex is the edge's target.  In the finished plan
+// (ginc) the INTERNAL edge id, the role in bit 31.
+FLAME_HD inline uint32_t inc_entry(int32_t e_orig, int role) { return ((uint32_t)e_orig << 1) | (uint32_t)role; }
+FLAME_HD inline int32_t inc_entry_edge(uint32_t x) { return (int32_t)(x >> 1); }
+FLAME_HD inline int inc_entry_role(uint32_t x) { return (int)(x & 1u); }
+FLAME_HD inline uint32_t inc_word(int32_t e_int, int role) { return (uint32_t)e_int | ((uint32_t)role << 31); }
+
 // ---- phase D of the tile kernels, as the lane order of a 64-edge block prices it (plan.cpp assign_lanes(), plan_dev.hip
 // assign_lanes_block()) ----
 // ds_read_b128 is served in 4 groups of 16 lanes: {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, and the same of lanes 32-63.

@@ -1046,14 +1046,14 @@ static int upload_device_plan(flame_hip_graph* g, const float* pos, const int32_
       }
     }
     bool ok = false, index_error = false;
-    int32_t uflags[4] = {0, 0, 0, 0};  // the finite-check word, the derived edge count (and the flags of an edge
+    int32_t uflags[kUserWords] = {0, 0, 0, 0};  // the finite-check word, the derived edge count (and the flags of an edge
                                        // derivation beside the build) ride on the builder's first sync
     g->planner.expect_edges(g->spec_edges ? E : -1);
     HIPCHK(g->planner.build(s, g->opt, V, E, T, ntiles, depth, in, &A, alloc_tile_arrays, &ctx, &tiles, &ok,
                             &index_error, g->dflags, uflags, after_order));
     g->planner.expect_edges(-1);
-    if (g->spec_edges && uflags[1] != E) { g->true_edges = uflags[1]; return 2; }  // the predicted edge count was wrong
-    if (uflags[0] & 1) return FLAME_HIP_ERR_NAN;
+    if (g->spec_edges && uflags[kUserEdgeCount] != E) { g->true_edges = uflags[kUserEdgeCount]; return 2; }  // the predicted edge count was wrong
+    if (uflags[kUserNonFinite] & kUserNonFiniteBit) return FLAME_HIP_ERR_NAN;
     if (index_error) return FLAME_HIP_ERR_ARG;
     const bool tiles_valid = ok;  // every tile was built (it may still be too large for LDS / a kernel config)
     if (ok) {

@@ -394,11 +394,7 @@ void order_vertices(const PlanOptions& opt, const float* pos, const std::vector<
       for (int a = 0; a < 2; ++a) { mn[a] = std::min(mn[a], pos[2 * v + a]); mx[a] = std::max(mx[a], pos[2 * v + a]); }
     std::vector<uint32_t>& code = P.b_code;
     code.resize(V);
-    for (int32_t v = 0; v < V; ++v) {
-      const uint32_t qx = (uint32_t)(65535.0f * (pos[2 * v] - mn[0]) / std::max(mx[0] - mn[0], 1e-20f));
-      const uint32_t qy = (uint32_t)(65535.0f * (pos[2 * v + 1] - mn[1]) / std::max(mx[1] - mn[1], 1e-20f));
-      code[v] = morton_spread16(qx) | (morton_spread16(qy) << 1);
-    }
+    for (int32_t v = 0; v < V; ++v) code[v] = morton_code(pos[2 * v], pos[2 * v + 1], mn[0], mn[1], mx[0], mx[1]);
     for (int t = 0; t < ntiles; ++t)
       std::sort(idx.begin() + leaf_start[t], idx.begin() + leaf_start[t + 1],
                 [&](int32_t a, int32_t b) { return code[a] != code[b] ? code[a] < code[b] : a < b; });
@@ -465,8 +461,7 @@ void order_edges(const PlanOptions& opt, const float* pos, const int32_t* edges,
     const int32_t e = eorder[k];
     const int32_t io = edges[2 * e], jo = edges[2 * e + 1];
     P.eij[k] = {P.v_o2i[io], P.v_o2i[jo]};
-    const float ds = opt.d_sign < 0 ? -1.0f : 1.0f;  // (a multiplication by +-1 is exact)
-    P.ew[k] = {alpha[e], beta[e], ds * (pos[2 * io] - pos[2 * jo]), ds * (pos[2 * io + 1] - pos[2 * jo + 1])};
+    P.ew[k] = edge_record<Float4>(alpha[e], beta[e], edge_dsign(opt.d_sign), pos[2 * io], pos[2 * io + 1], pos[2 * jo], pos[2 * jo + 1]);
   }
 }
 
@@ -480,8 +475,8 @@ void build_incidence(Plan& P) {
   std::vector<int32_t> fill(P.grow.begin(), P.grow.end() - 1);
   for (int32_t eo = 0; eo < E; ++eo) {  // original order => each list ascending in original id
     const int32_t k = P.e_o2i[eo];
-    P.ginc[fill[P.eij[k].x]++] = k;
-    P.ginc[fill[P.eij[k].y]++] = k | (int32_t)0x80000000;
+    P.ginc[fill[P.eij[k].x]++] = (int32_t)inc_word(k, 0);
+    P.ginc[fill[P.eij[k].y]++] = (int32_t)inc_word(k, 1);
   }
 }
 

@@ -26,6 +26,48 @@ namespace flamehip {
 
 int test_alloc_fill();  // flame_hip.cpp: the byte new device allocations are filled with in the hooks library, else -1
 
+// Bits of the builder's flag word (flags_[0]; words 1..3 hold the tile-array totals, word 4 the edge count of a
+// synchronous edges_from_tris).  Raised by the kernels, decoded once by plan_verdict().
+enum PlanFlag : int32_t {
+  kPlanBadPartition = 1,      // the segment table is not one leaf per tile, in tile order
+  kPlanBadIndex = 2,          // an edge / triangle index out of range (or a degenerate edge)
+  kPlanTileTooLarge = 4,      // a tile above the order cap, or beyond every kernel configuration
+  kPlanTilePassFailed = 8,    // a tile pass gave up on a tile (its descriptor says n_ext = -1)
+  kPlanSubtreeOverflow = 16,  // a subtree outgrew its workgroup: hand over one level later
+  kPlanLookbackTimeout = 32,  // a single-launch scan's look-back timed out (never seen)
+  kPlanReuseRejected = 64,    // the previous frame's partition does not suit this frame
+  kPlanSpecTooSmall = 128,    // the speculatively sized tile arrays were too small: run pass 2 again
+};
+// What a flag word says about a build.  The order of the tests matters: a timed-out scan makes every later stage's output
+// (and flags) meaningless, a rejected reuse explains the bad index or the oversized tile behind it, and so on.
+enum class PlanVerdict {
+  kOk,
+  kIndexError,     // the caller's graph is wrong
+  kRetrySubtree,   // bisect again, handing over to the subtree kernel one level later
+  kSpecTooSmall,   // the totals are exact now: allocate for them and run pass 2 again
+  kTileFailed,     // rejected by a tile pass; the totals are valid all the same
+  kRejected,       // not ok: the caller retries with smaller tiles or builds on the host
+  kRejectedReuse,  // ... and the previous frame's tile map goes with it
+};
+inline PlanVerdict plan_verdict(int32_t f) {
+  if (f & kPlanLookbackTimeout) return PlanVerdict::kRejected;
+  if (f & kPlanReuseRejected) return PlanVerdict::kRejectedReuse;
+  if (f & kPlanBadIndex) return PlanVerdict::kIndexError;
+  if (f & kPlanSubtreeOverflow) return PlanVerdict::kRetrySubtree;
+  if (f & (kPlanBadPartition | kPlanTileTooLarge)) return PlanVerdict::kRejected;
+  if (f & kPlanSpecTooSmall) return PlanVerdict::kSpecTooSmall;
+  return (f & kPlanTilePassFailed) ? PlanVerdict::kTileFailed : PlanVerdict::kOk;
+}
+
+// The caller's words (build()'s user_flags_dev / user_flags_host, edges_from_tris()'s nan_flag, MiniSync::dflags)
+enum UserWord : int {
+  kUserNonFinite = 0,   // kUserNonFiniteBit: a derived or uploaded value is not finite
+  kUserEdgeCount = 1,   // the number of edges the graph sync derived
+  kUserChainFlags = 2,  // the edge chain's own flags: kPlanBadIndex, kPlanLookbackTimeout
+  kUserWords = 4,
+};
+constexpr int32_t kUserNonFiniteBit = 1;
+
 // Device arrays of a plan.  Owned by the caller (the handle), sized by the caller:
 // V / E / T sized arrays before build, the tile arrays through `alloc_tiles` once their sizes are
 // known (after the first per-tile pass).
@@ -160,6 +202,19 @@ class DevPlanner {
   bool last_build_reused() const { return last_reused_; }
 
  private:
+  // build() = these stages in this order (plan_dev.hip); Build: what they share
+  struct Build;
+  void partition_mini(Build& b);          // A (to E) by one launch of one workgroup
+  void partition_reuse(Build& b);         // A from the previous frame's tile map
+  hipError_t partition_bisect(Build& b);  // A by exact bisection, with the subtree hand-over
+  void order_vertices(Build& b);          // B
+  hipError_t triangle_csr(Build& b);      // E, on the second stream
+  hipError_t edge_order(Build& b);        // C
+  hipError_t incidence_csr(Build& b);     // D
+  hipError_t tile_passes(Build& b);       // F: fused, or pass 1 + offsets (+ pass 2)
+  hipError_t launch_pass2(Build& b);
+  hipError_t publish(Build& b);
+  hipError_t rerun_pass2(Build& b, bool spec_too_small);  // G
   hipError_t reserve(int32_t V, int32_t E, int32_t T, int ntiles);
   hipError_t scan_i32(hipStream_t s, int lane, const int32_t* in, int32_t* out, int64_t n, bool inclusive,
                       void* cub_tmp, size_t cub_bytes);

@@ -1,5 +1,7 @@
 // flame_ros_amd/csrc/plan_dev.hip -- see plan_dev.h.  The graph plan built by HIP kernels
-// (SURVEY.md 8f row f3).  Stage by stage the same rules as plan.cpp, so the arrays are identical:
+// (SURVEY.md 8f row f3).  Stage by stage the same rules as plan.cpp, so the arrays are identical: the per-element rules are
+// single functions (common.h and below; DESIGN.md 5.2 lists them) that the host builder, the staged kernels and k_mini_plan
+// call.  DevPlanner::build() is the list of these stages, one member function each:
 //
 //   A  partition     recursive coordinate bisection on two PRESORTED lists (the vertex ids along x and
 //                    along y, total order (coordinate, id)): per level the box of a segment is the two
@@ -21,7 +23,7 @@
 // partition of a frame from the previous frame's tile map (k_reuse_*, "Partition REUSE"), the counting
 // passes' atomics doubling as ranks, fused launches (k_he_unique, k_edge_rows_gather, k_tile_fused,
 // k_publish) and, for frames of up to 2 k vertices, everything in front of the tile pass in one
-// launch of one workgroup (k_mini_plan).
+// launch of one workgroup (k_mini_plan): other traversals of the data, the same statements of the rules.
 // Library code: rocprim's device radix sort (the two entry sorts), device scan, block radix sort, called directly (r05:
 // no hipcub veneer).  rocprim
 // sorts fewer than ~1 M keys by block sort + log2 merge passes (7 launches for 50 k keys, 19 for
@@ -135,7 +137,6 @@ __global__ __launch_bounds__(1024) void k_rcb_bbox(const int32_t* __restrict__ n
   }
 }
 
-
 __global__ void k_save_gbbox(const uint32_t* bbox, float* gbbox) {
   if (threadIdx.x < 4) gbbox[threadIdx.x] = unord_f(bbox[threadIdx.x]);
 }
@@ -150,9 +151,6 @@ __global__ __launch_bounds__(256) void k_rank_keys(int32_t V, const float2* __re
   keys[v] = ord_f(axis ? q.y : q.x);  // the (stable) radix sort breaks ties by input order = id
   vals[v] = (uint32_t)v;
 }
-
-
-
 
 // first position m of the segment with (2 acc(m) + w_m) leaves >= 2 total l1 (plan.cpp split_range)
 __global__ __launch_bounds__(256) void k_rcb_mid(int32_t V, const int32_t* __restrict__ seg_pos, SegTab t,
@@ -235,8 +233,6 @@ __global__ __launch_bounds__(kSegCap) void k_rcb_split(const int32_t* nseg_cur, 
   bbox[4 * s + 2] = bbox[4 * s + 3] = 0u;
 }
 
-
-
 // several scratch arrays zeroed by ONE launch (a build had a dozen separate memsets)
 constexpr int kZeroJobs = 5;
 struct ZeroJob { int32_t* p[kZeroJobs]; int64_t n[kZeroJobs]; };
@@ -271,7 +267,6 @@ __device__ __forceinline__ T block_exclusive(T v, T* a) {
   __syncthreads();
   return base + inc - v;
 }
-
 
 // ------------------------------------------------------------------------------------------
 // Single-launch prefix sums.  The library's device scan is two launches (look-back state init + scan) and
@@ -308,7 +303,7 @@ __device__ __forceinline__ T scan_lookback(T block_total, const ScanState& st, T
       int spin = 0;
       while (__hip_atomic_load(&st.flag[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != st.epoch) {
         __builtin_amdgcn_s_sleep(1);
-        if (++spin > (1 << 22)) { atomicOr(st.err, 32); break; }
+        if (++spin > (1 << 22)) { atomicOr(st.err, kPlanLookbackTimeout); break; }
       }
       acc += (T)__hip_atomic_load(&st.agg[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -500,7 +495,7 @@ __global__ __launch_bounds__(kSubThreads) void k_rcb_subtree(const int32_t* nseg
     // Until then the later stages still run on this partition, so leave a VALID one behind (the
     // segment cut into equal runs of the current order) -- stale table contents here sent the
     // tile kernels out of bounds.
-    if (tid == 0) atomicOr(&flags[0], 16);
+    if (tid == 0) atomicOr(&flags[0], kPlanSubtreeOverflow);
     for (int j = tid; j < gleaves; j += kSubThreads) {
       const int32_t a = glo + (int32_t)(((long long)n * j) / gleaves);
       const int32_t b = glo + (int32_t)(((long long)n * (j + 1)) / gleaves);
@@ -736,8 +731,8 @@ __global__ __launch_bounds__(kSubThreads) void k_rcb_subtree(const int32_t* nseg
 // after the last level: every segment is one tile, in tile order
 __global__ __launch_bounds__(kSegCap) void k_rcb_check(const int32_t* nseg, SegTab t, int32_t ntiles, int32_t* flags) {
   const int s = threadIdx.x;
-  if (s == 0 && nseg[0] != ntiles) atomicOr(&flags[0], 1);
-  if (s < ntiles && (t.leaves[s] != 1 || t.first[s] != s)) atomicOr(&flags[0], 1);
+  if (s == 0 && nseg[0] != ntiles) atomicOr(&flags[0], kPlanBadPartition);
+  if (s < ntiles && (t.leaves[s] != 1 || t.first[s] != s)) atomicOr(&flags[0], kPlanBadPartition);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -756,7 +751,7 @@ __global__ __launch_bounds__(256) void k_tile_order(int32_t V, int32_t ntiles, c
   const int32_t lo = max(0, min(tlo[t], V)), hi = max(lo, min(thi[t], V));  // (tables of a rejected
   const int n = hi - lo;                                                    //  partition stay in range)
   if (n > kOrderCap) {  // cannot be a tile of any kernel configuration: keep the order, flag the plan
-    if (tid == 0) atomicOr(&flags[0], 4);
+    if (tid == 0) atomicOr(&flags[0], kPlanTileTooLarge);
     for (int p = tid; p < n; p += 256) { const int32_t v = v_i2o[lo + p]; v_o2i[v] = lo + p; tile_of_int[lo + p] = t; }
     return;
   }
@@ -767,11 +762,7 @@ __global__ __launch_bounds__(256) void k_tile_order(int32_t V, int32_t ntiles, c
     if (p < n) {
       const int32_t v = v_i2o[lo + p];
       const float2 q = pos[v];
-      // (clamped: identity for a box that is this frame's own; a reused partition keeps the box of
-      // the frame it was made from)
-      const uint32_t qx = (uint32_t)(65535.0f * (fminf(fmaxf(q.x, mnx), mxx) - mnx) / fmaxf(mxx - mnx, 1e-20f));
-      const uint32_t qy = (uint32_t)(65535.0f * (fminf(fmaxf(q.y, mny), mxy) - mny) / fmaxf(mxy - mny, 1e-20f));
-      k = ((uint64_t)(morton_spread16(qx) | (morton_spread16(qy) << 1)) << 32) | (uint32_t)v;
+      k = morton_key(morton_code(q.x, q.y, mnx, mny, mxx, mxy), v);
     }
     keys[p] = k;
   }
@@ -793,18 +784,21 @@ __global__ __launch_bounds__(256) void k_tile_order(int32_t V, int32_t ntiles, c
 // i.e. index 2 lo_t + (cross ? n_t : 0) + (u - lo_t).  Count, exclusive scan, fill through a cursor,
 // every bucket sorted by original edge id (k_csr_rows): the order the stable sort on
 // (tile, cross, source) gave, in 7 short launches instead of a 9-launch merge sort of E keys.
+__device__ __forceinline__ int32_t edge_bucket_of(int32_t si, int32_t ti, int32_t tj, int32_t lo, int32_t n) {
+  return 2 * lo + (ti == tj ? 0 : n) + (si - lo);  // si, sj: internal ends in tiles ti, tj; tile ti owns [lo, lo + n)
+}
 __device__ __forceinline__ int32_t edge_bucket(const int2 ij, int32_t V, const int32_t* __restrict__ v_o2i,
                                                const int32_t* __restrict__ tile_of_int,
                                                const int32_t* __restrict__ tlo, const int32_t* __restrict__ thi,
                                                int32_t* flags) {
   if (ij.x < 0 || ij.y < 0 || ij.x >= V || ij.y >= V || ij.x == ij.y) {  // build_plan's index check
-    if (flags) atomicOr(&flags[0], 2);
+    if (flags) atomicOr(&flags[0], kPlanBadIndex);
     return 0;
   }
   const int32_t si = v_o2i[ij.x], sj = v_o2i[ij.y];
   const int32_t ti = tile_of_int[si], tj = tile_of_int[sj];
-  const int32_t lo = tlo[ti], n = thi[ti] - lo;
-  return 2 * lo + (ti == tj ? 0 : n) + (si - lo);
+  const int32_t lo = tlo[ti];
+  return edge_bucket_of(si, ti, tj, lo, thi[ti] - lo);
 }
 
 __global__ __launch_bounds__(256) void k_edge_count(int32_t E, int32_t V, const int2* __restrict__ edges,
@@ -832,9 +826,6 @@ __global__ __launch_bounds__(256) void k_edge_fill(int32_t E, int32_t V, const i
   out[off[b] + rank[e]] = (uint32_t)e;
 }
 
-
-
-
 // ------------------------------------------------------------------------------------------
 // Stage D / E: incidence CSR (ascending ORIGINAL edge id per vertex), triangle CSR
 // ------------------------------------------------------------------------------------------
@@ -853,8 +844,8 @@ __global__ __launch_bounds__(256) void k_csr_fill(int32_t E, const int2* __restr
   if (e >= E) return;
   const int2 ij = eij[e_o2i[e]];
   const int2 r = rank[e];
-  out[row[ij.x] + r.x] = (uint32_t)e << 1;
-  out[row[ij.y] + r.y] = ((uint32_t)e << 1) | 1u;
+  out[row[ij.x] + r.x] = inc_entry(e, 0);
+  out[row[ij.y] + r.y] = inc_entry(e, 1);
 }
 
 __global__ __launch_bounds__(256) void k_tri_count(int32_t n3, int32_t V, const int32_t* __restrict__ tris,
@@ -863,7 +854,7 @@ __global__ __launch_bounds__(256) void k_tri_count(int32_t n3, int32_t V, const 
   const int32_t k = blockIdx.x * 256 + threadIdx.x;
   if (k >= n3) return;
   const int32_t vo = tris[k];
-  if (vo < 0 || vo >= V) { atomicOr(&flags[0], 2); tris_int[k] = 0; return; }
+  if (vo < 0 || vo >= V) { atomicOr(&flags[0], kPlanBadIndex); tris_int[k] = 0; return; }
   const int32_t v = v_o2i[vo];
   tris_int[k] = v;
   rank[k] = atomicAdd(&cnt[v], 1);
@@ -883,7 +874,7 @@ __global__ __launch_bounds__(256) void k_tri_fill(int32_t n3, int32_t V, const i
 
 // one thread per row: ascending order (insertion sort; heap sort for long rows, so that a vertex of
 // huge degree costs d log d, not d^2), the rows of a block staged in LDS when they fit; CONVERT: entries (original edge id << 1 | role) become
-// (internal edge id | role << 31)
+// (internal edge id, role in bit 31: inc_word())
 __device__ __forceinline__ void sort_row(uint32_t* a, int d) {
   if (d <= 24) {
     for (int i = 1; i < d; ++i) {
@@ -912,35 +903,50 @@ __device__ __forceinline__ void sort_row(uint32_t* a, int d) {
 }
 
 constexpr int kRowsLds = 6144;  // entries of 256 consecutive rows staged in LDS (else sorted in place)
+// The 256 consecutive rows of a block are one contiguous range [r0, r1) of the array: staged in LDS when they fit, so that
+// every thread sorts its own row there (else in place)
+struct BlockRows { int32_t r0, r1; bool lds; };
+__device__ __forceinline__ BlockRows stage_block_rows(uint32_t* s_a, const int32_t* __restrict__ row, const uint32_t* arr, int32_t nrows) {
+  const int32_t v0 = blockIdx.x * 256, v1 = min(v0 + 256, nrows);
+  BlockRows b;
+  b.r0 = row[v0]; b.r1 = row[v1];
+  b.lds = b.r1 - b.r0 <= kRowsLds;
+  if (b.lds) {
+    for (int32_t i = threadIdx.x; i < b.r1 - b.r0; i += 256) s_a[i] = arr[b.r0 + i];
+    __syncthreads();
+  }
+  return b;
+}
+__device__ __forceinline__ uint32_t* block_row(const BlockRows& b, uint32_t* s_a, uint32_t* arr, int32_t start) {
+  return b.lds ? s_a + (start - b.r0) : arr + start;
+}
 // CONVERT also leaves, for the tile passes: gadj[s] = the vertex at the other end of incidence s (the
 // ring search then needs two dependent loads per step, not three) and ipos[2k + role] = the place of
 // internal edge k in the row of its source (role 0) / target (role 1) (the slot of an incidence
 // without a search).
+__device__ __forceinline__ int32_t inc_other_end(int role, int32_t src, int32_t dst) { return role ? src : dst; }
+__device__ __forceinline__ int32_t ipos_index(int32_t e_int, int role) { return 2 * e_int + role; }
 template <bool CONVERT>
 __global__ __launch_bounds__(256) void k_csr_rows(int32_t V, const int32_t* __restrict__ row,
                                                   const int32_t* __restrict__ e_o2i, uint32_t* out,
                                                   const int2* __restrict__ eij = nullptr, int32_t* gadj = nullptr,
                                                   int32_t* ipos = nullptr) {
   __shared__ uint32_t s_a[kRowsLds];
-  const int32_t v0 = blockIdx.x * 256, v1 = min(v0 + 256, V);
-  const int32_t r0 = row[v0], r1 = row[v1];
-  const int32_t v = v0 + threadIdx.x;
-  const bool lds = r1 - r0 <= kRowsLds;  // the block's rows are one contiguous range of the array
-  if (lds) {
-    for (int32_t i = threadIdx.x; i < r1 - r0; i += 256) s_a[i] = out[r0 + i];
-    __syncthreads();
-  }
+  const BlockRows b = stage_block_rows(s_a, row, out, V);
+  const int32_t r0 = b.r0, r1 = b.r1;
+  const int32_t v = blockIdx.x * 256 + threadIdx.x;
+  const bool lds = b.lds;
   if (v < V) {
     const int d = row[v + 1] - row[v];
-    uint32_t* a = lds ? s_a + (row[v] - r0) : out + row[v];
+    uint32_t* a = lds ? s_a + (row[v] - r0) : out + row[v];  // = block_row(), which costs this kernel 2 SGPRs
     sort_row(a, d);
     if (CONVERT && gadj) {
       for (int i = 0; i < d; ++i) {
         const uint32_t x = a[i];
-        const int32_t k = e_o2i[x >> 1];
+        const int32_t k = e_o2i[inc_entry_edge(x)];
         const int2 ij = eij[k];
-        gadj[row[v] + i] = (x & 1u) ? ij.x : ij.y;
-        ipos[2 * k + (int32_t)(x & 1u)] = i;
+        gadj[row[v] + i] = inc_other_end(inc_entry_role(x), ij.x, ij.y);
+        ipos[ipos_index(k, inc_entry_role(x))] = i;
       }
     }
   }
@@ -948,18 +954,17 @@ __global__ __launch_bounds__(256) void k_csr_rows(int32_t V, const int32_t* __re
     __syncthreads();
     for (int32_t i = threadIdx.x; i < r1 - r0; i += 256) {
       const uint32_t x = s_a[i];
-      out[r0 + i] = CONVERT ? ((uint32_t)e_o2i[x >> 1] | ((x & 1u) << 31)) : x;
+      out[r0 + i] = CONVERT ? inc_word(e_o2i[inc_entry_edge(x)], inc_entry_role(x)) : x;
     }
   } else if (CONVERT && v < V) {
     uint32_t* a = out + row[v];
     const int d = row[v + 1] - row[v];
     for (int i = 0; i < d; ++i) {
       const uint32_t x = a[i];
-      a[i] = (uint32_t)e_o2i[x >> 1] | ((x & 1u) << 31);
+      a[i] = inc_word(e_o2i[inc_entry_edge(x)], inc_entry_role(x));
     }
   }
 }
-
 
 // Stage C's last two launches and stage D's first in one: a block sorts its 256 buckets in LDS
 // (as k_csr_rows does), then writes the edge records of exactly those entries and counts the degrees of
@@ -974,15 +979,11 @@ __global__ __launch_bounds__(256) void k_edge_rows_gather(int32_t nrows, const i
                                                           int32_t ntiles, const int32_t* __restrict__ tlo,
                                                           int32_t* estart, float dsign, int32_t* deg_cnt, int2* rank2) {
   __shared__ uint32_t s_a[kRowsLds];
-  const int32_t v0 = blockIdx.x * 256, v1 = min(v0 + 256, nrows);
-  const int32_t r0 = off[v0], r1 = off[v1];
-  const int32_t v = v0 + threadIdx.x;
-  const bool lds = r1 - r0 <= kRowsLds;  // the block's rows are one contiguous range of the array
-  if (lds) {
-    for (int32_t i = threadIdx.x; i < r1 - r0; i += 256) s_a[i] = sorted_e[r0 + i];
-    __syncthreads();
-  }
-  if (v < nrows) sort_row(lds ? s_a + (off[v] - r0) : sorted_e + off[v], off[v + 1] - off[v]);
+  const int32_t v = blockIdx.x * 256 + threadIdx.x;
+  const BlockRows b = stage_block_rows(s_a, off, sorted_e, nrows);
+  const int32_t r0 = b.r0, r1 = b.r1;
+  const bool lds = b.lds;
+  if (v < nrows) sort_row(block_row(b, s_a, sorted_e, off[v]), off[v + 1] - off[v]);
   __syncthreads();
   // estart[t] = first internal edge owned by tile t = where its first bucket starts
   const int32_t g = blockIdx.x * 256 + threadIdx.x;
@@ -1007,7 +1008,7 @@ __global__ __launch_bounds__(256) void k_edge_rows_gather(int32_t nrows, const i
     const int32_t si = v_o2i[ij.x], sj = v_o2i[ij.y];
     const float2 pi = pos[ij.x], pj = pos[ij.y];
     eij[k] = make_int2(si, sj);
-    ew[k] = make_float4(alpha[e], beta[e], dsign * (pi.x - pj.x), dsign * (pi.y - pj.y));
+    ew[k] = edge_record<float4>(alpha[e], beta[e], dsign, pi.x, pi.y, pj.x, pj.y);
     int2 r;
     r.x = atomicAdd(&deg_cnt[si], 1);
     r.y = atomicAdd(&deg_cnt[sj], 1);
@@ -1044,7 +1045,6 @@ __device__ __forceinline__ int32_t hash_lookup(const TileLds& L, int32_t gid) {
   }
   return -1;
 }
-
 
 constexpr int kRowLanes = 4;  // threads per incidence row in the tile passes
 
@@ -1194,7 +1194,7 @@ __global__ __launch_bounds__(kSegCap) void k_tile_offsets(int ntiles, int32_t* m
   if (t < ntiles) {
     const int32_t* m = meta + (size_t)t * kMetaWords;
     v[0] = m[0]; v[1] = m[1]; v[2] = m[2];
-    if (m[3]) atomicOr(&flags[0], 4);
+    if (m[3]) atomicOr(&flags[0], kPlanTileTooLarge);
   }
   for (int c = 0; c < 3; ++c) sc[c][t] = v[c];
   __syncthreads();
@@ -1212,7 +1212,7 @@ __global__ __launch_bounds__(kSegCap) void k_tile_offsets(int ntiles, int32_t* m
   if (t == kSegCap - 1) {
     flags[1] = sc[0][t]; flags[2] = sc[1][t]; flags[3] = sc[2][t];
     // speculative tile arrays (sized from the previous frame, no host round trip before pass 2): too small?
-    if (cap_nv > 0 && (sc[0][t] > cap_nv || sc[1][t] > cap_ne || sc[2][t] > cap_ns)) atomicOr(&flags[0], 128);
+    if (cap_nv > 0 && (sc[0][t] > cap_nv || sc[1][t] > cap_ne || sc[2][t] > cap_ns)) atomicOr(&flags[0], kPlanSpecTooSmall);
   }
 }
 
@@ -1488,7 +1488,7 @@ __device__ __forceinline__ void tile_emit(const TileGraph& G, const TileLds& L, 
     D.vmap_off = voff; D.emap_off = eoff; D.erec_off = eoff; D.srow_off = soff;
     D.nslots = S.gbase[kCapExt / 64];
     for (int r = 0; r <= kMaxDepth; ++r) { D.ring_end[r] = S.ring_end[r]; D.level_end[r] = S.level_end[r]; }
-    if (S.fail) { D.n_ext = -1; atomicOr(&O.flags[0], 8); }
+    if (S.fail) { D.n_ext = -1; atomicOr(&O.flags[0], kPlanTilePassFailed); }
     O.tiles[t] = D;
   }
 }
@@ -1505,7 +1505,7 @@ __global__ __launch_bounds__(kP2Threads) void k_tile_pass2(TileGraph G, const in
   // a build that has already failed (bad indices, a tile that does not fit, a rejected partition, tile
   // arrays too small for a speculative launch: every bit but pass 2's own 8) must not be continued:
   // the host used to stop before this launch; without the round trip the kernel stops itself
-  if (__builtin_amdgcn_readfirstlane(O.flags[0]) & ~8) return;
+  if (__builtin_amdgcn_readfirstlane(O.flags[0]) & ~kPlanTilePassFailed) return;
   TileLds L;
   int32_t* cnt = reinterpret_cast<int32_t*>(smem);               // kBucketInts
   L.bitmap = reinterpret_cast<uint32_t*>(cnt + kBucketInts);
@@ -1559,7 +1559,7 @@ __global__ __launch_bounds__(kP2Threads) void k_tile_fused(TileGraph G, const in
   // the tiles behind it wait for its totals)
   // (it still publishes: a flag raised by the second stream while this launch runs is seen by some
   // tiles and not by others)
-  if (__builtin_amdgcn_readfirstlane(O.flags[0]) & ~(4 | 8 | 128)) {
+  if (__builtin_amdgcn_readfirstlane(O.flags[0]) & ~(kPlanTileTooLarge | kPlanTilePassFailed | kPlanSpecTooSmall)) {
     if (tid == 0) {
       __hip_atomic_store(&st.agg[t], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1602,11 +1602,11 @@ __global__ __launch_bounds__(kP2Threads) void k_tile_fused(TileGraph G, const in
   if (tid == 0) {
     m[0] = n_ext; m[1] = e_cnt; m[2] = n_upd; m[3] = bad ? 1 : 0;
     m[21] = voff; m[22] = eoff; m[23] = soff;
-    if (bad) atomicOr(&O.flags[0], 4);
+    if (bad) atomicOr(&O.flags[0], kPlanTileTooLarge);
     if (t == ntiles - 1) { O.flags[1] = voff + n_ext; O.flags[2] = eoff + e_loc; O.flags[3] = soff + n_upd; }
   }
   const bool over = voff + n_ext > cap_nv || eoff + e_loc > cap_ne || soff + n_upd > cap_ns;
-  if (over && tid == 0) atomicOr(&O.flags[0], 128);
+  if (over && tid == 0) atomicOr(&O.flags[0], kPlanSpecTooSmall);
   if (bad || over) {
     if (tid == 0 && bad && !over) { TileDesc D = {}; D.n_ext = -1; O.tiles[t] = D; }
     return;
@@ -1682,20 +1682,24 @@ __device__ __forceinline__ int pyr_cell(const float* b, float2 q, int level) {
   return kPyrOff[level] + cy * d + cx;
 }
 
-// tile of every vertex of the NEW frame from the previous frame's pyramid; tile counts
+// tile of a vertex of the NEW frame from the previous frame's pyramid: the finest non-empty level, clamped
+__device__ __forceinline__ int32_t reuse_tile(const float* bounds, const int32_t* __restrict__ pyr, float2 q, int32_t ntiles) {
+  int32_t t = 0;
+  for (int l = 0; l < kPyrLevels; ++l) {
+    const int32_t c = pyr[pyr_cell(bounds, q, l)];
+    if (c > 0) { t = c - 1; break; }
+  }
+  return max(0, min(t, ntiles - 1));
+}
+
+// ... of every vertex; tile counts
 __global__ __launch_bounds__(256) void k_reuse_assign(int32_t V, int32_t ntiles, const float2* __restrict__ pos,
                                                       const float* __restrict__ bounds,
                                                       const int32_t* __restrict__ pyr, int32_t* vt, int32_t* vrank,
                                                       int32_t* tile_cnt) {
   const int32_t v = blockIdx.x * 256 + threadIdx.x;
   if (v >= V) return;
-  const float2 q = pos[v];
-  int32_t t = 0;
-  for (int l = 0; l < kPyrLevels; ++l) {
-    const int32_t c = pyr[pyr_cell(bounds, q, l)];
-    if (c > 0) { t = c - 1; break; }
-  }
-  t = max(0, min(t, ntiles - 1));
+  const int32_t t = reuse_tile(bounds, pyr, pos[v], ntiles);
   // the count doubles as the vertex's rank inside its tile (any order will do: stage B sorts the tile),
   // so the scatter needs no second round of contended atomics.  One counter per 128-byte line: a
   // few hundred counters packed into 8 lines serialise every atomic of the launch on 8 L2 channels
@@ -1734,11 +1738,11 @@ __global__ __launch_bounds__(256) void k_reuse_scatter(int32_t V, int32_t ntiles
       if (i < ntiles) {
         const int32_t lo = s_lo[i];
         t.lo[i] = lo; t.hi[i] = lo + c[k]; t.leaves[i] = 1; t.first[i] = i;
-        if (c[k] < 1 || c[k] > cap) atomicOr(&flags[0], 64);
+        if (c[k] < 1 || c[k] > cap) atomicOr(&flags[0], kPlanReuseRejected);
       }
     }
     if (tid == 0) nseg[0] = ntiles;
-    if (tid == 255 && run != V) atomicOr(&flags[0], 64);
+    if (tid == 255 && run != V) atomicOr(&flags[0], kPlanReuseRejected);
   }
   __syncthreads();
   const int32_t v = blockIdx.x * 256 + tid;
@@ -1817,7 +1821,6 @@ __global__ __launch_bounds__(1024) void k_grid_final(int32_t V, const unsigned l
   grid_w[c] = cnt[c] > 0 ? (int32_t)((long long)sum[c] / cnt[c]) : mean;
 }
 
-
 // ------------------------------------------------------------------------------------------
 // Graph sync on the device (row a7 / f3): the unique undirected edges of a triangulation, i < j, in
 // lexicographic order, with alpha = 1 / |pos_i - pos_j| (statement: oracle nltgv2_graph_sync).
@@ -1829,9 +1832,7 @@ __global__ __launch_bounds__(1024) void k_grid_final(int32_t V, const unsigned l
 // 3T 64-bit keys gave, in 9 short launches instead of ~24.
 __device__ __forceinline__ bool half_edge(int32_t k, int32_t V, const int32_t* __restrict__ tris, int32_t* a, int32_t* b) {
   const int32_t t = k / 3, c = k - 3 * t;
-  const int32_t u = tris[3 * t + c], w = tris[3 * t + (c == 2 ? 0 : c + 1)];
-  *a = min(u, w); *b = max(u, w);
-  return !(u < 0 || w < 0 || u >= V || w >= V || u == w);
+  return tri_side(tris[3 * t + c], tris[3 * t + (c == 2 ? 0 : c + 1)], V, a, b);
 }
 
 __global__ __launch_bounds__(256) void k_he_count(int32_t n3, int32_t V, const int32_t* __restrict__ tris, int32_t* cnt,
@@ -1839,7 +1840,7 @@ __global__ __launch_bounds__(256) void k_he_count(int32_t n3, int32_t V, const i
   const int32_t k = blockIdx.x * 256 + threadIdx.x;
   if (k >= n3) return;
   int32_t a, b;
-  if (!half_edge(k, V, tris, &a, &b)) { atomicOr(&flags[0], 2); return; }
+  if (!half_edge(k, V, tris, &a, &b)) { atomicOr(&flags[0], kPlanBadIndex); return; }
   rank[k] = atomicAdd(&cnt[a], 1);
 }
 
@@ -1874,9 +1875,9 @@ __global__ __launch_bounds__(256) void k_he_compact(int32_t V, const int32_t* __
     const float2 pj = pos[j];
     const float dx = pi.x - pj.x, dy = pi.y - pj.y;
     edges[idx[k]] = make_int2(v, j);
-    const float a = 1.0f / sqrtf(dx * dx + dy * dy);  // -ffp-contract=off: two roundings, as the oracle
+    const float a = edge_alpha(dx, dy);
     alpha[idx[k]] = a;
-    if (nan_flag && !isfinite(a)) atomicOr(nan_flag, 1);  // (two features on one pixel)
+    if (nan_flag && !isfinite(a)) atomicOr(&nan_flag[kUserNonFinite], kUserNonFiniteBit);  // (two features on one pixel)
   }
 }
 
@@ -1889,19 +1890,13 @@ __global__ __launch_bounds__(256) void k_he_unique(int32_t V, const int32_t* __r
   __shared__ uint32_t s_a[kRowsLds];
   __shared__ int32_t sh_a[16];
   __shared__ int32_t sh_p[2];
-  const int32_t v0 = blockIdx.x * 256, v1 = min(v0 + 256, V);
-  const int32_t r0 = off[v0], r1 = off[v1];
-  const int32_t v = v0 + threadIdx.x;
-  const bool lds = r1 - r0 <= kRowsLds;
-  if (lds) {
-    for (int32_t i = threadIdx.x; i < r1 - r0; i += 256) s_a[i] = out[r0 + i];
-    __syncthreads();
-  }
+  const int32_t v = blockIdx.x * 256 + threadIdx.x;
+  const BlockRows b = stage_block_rows(s_a, off, out, V);
   int d = 0, uniq = 0;
   uint32_t* a = nullptr;
   if (v < V) {
     d = off[v + 1] - off[v];
-    a = lds ? s_a + (off[v] - r0) : out + off[v];
+    a = block_row(b, s_a, out, off[v]);
     sort_row(a, d);
     for (int k = 0; k < d; ++k) uniq += (k == 0 || a[k] != a[k - 1]) ? 1 : 0;
   }
@@ -1918,9 +1913,9 @@ __global__ __launch_bounds__(256) void k_he_unique(int32_t V, const int32_t* __r
     const float2 pj = pos[j];
     const float dx = pi.x - pj.x, dy = pi.y - pj.y;
     edges[idx] = make_int2(v, j);
-    const float al = 1.0f / sqrtf(dx * dx + dy * dy);  // -ffp-contract=off: two roundings, as the oracle
+    const float al = edge_alpha(dx, dy);
     alpha[idx] = al;
-    if (nan_flag && !isfinite(al)) atomicOr(nan_flag, 1);  // (two features on one pixel)
+    if (nan_flag && !isfinite(al)) atomicOr(&nan_flag[kUserNonFinite], kUserNonFiniteBit);  // (two features on one pixel)
     ++idx;
   }
   if (v == V - 1) total[0] = idx;
@@ -1932,6 +1927,8 @@ __global__ __launch_bounds__(256) void k_sync_data(int32_t V, const float* __res
                                                    float* x0, int32_t* nan_flag) {
   const int32_t v = blockIdx.x * 256 + threadIdx.x;
   if (v >= V) return;
+  // = data_term() / data_term_finite() (common.h), spelled out: through the helper the loads of var / pred leave their
+  // branches and the kernel takes one more SGPR (value arguments) or VGPR (element pointers)
   const float zi = mu[v] / scale;
   const float wi = adaptive ? 1.0f / var[v] : 1.0f;
   const float xi = (init_pred && pred && isfinite(pred[v])) ? pred[v] / scale : zi;
@@ -1939,7 +1936,7 @@ __global__ __launch_bounds__(256) void k_sync_data(int32_t V, const float* __res
   wgt[v] = wi;
   x0[v] = xi;
   // the non-finite-input check of the upload rides here (it was three more launches per frame)
-  if (nan_flag && !(isfinite(zi) && isfinite(wi) && isfinite(xi))) atomicOr(nan_flag, 1);
+  if (nan_flag && !(isfinite(zi) && isfinite(wi) && isfinite(xi))) atomicOr(&nan_flag[kUserNonFinite], kUserNonFiniteBit);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1947,10 +1944,12 @@ __global__ __launch_bounds__(256) void k_sync_data(int32_t V, const float* __res
 // the tile pass -- edges of the triangulation, data terms, partition from the previous frame's tile
 // map, vertex order, triangle CSR, edge order, incidence CSR -- in ONE launch of ONE workgroup.
 // At 1.2 k vertices those stages were 24 dependent launches whose kernels run 2-5 us each: ~0.15 ms
-// of a 0.55 ms frame was the dependency latency between them.  Same rules, same arrays as the
-// stages above (k_he_*, k_sync_data, k_reuse_*, k_tile_order, k_tri_*, k_edge_*, k_csr_*): the phases
-// below are those kernels' bodies as loops over one workgroup, counters and offsets in LDS,
-// __syncthreads() between them.  tests/test_gpu_plan_device.py compares the two paths array for array.
+// of a 0.55 ms frame was the dependency latency between them.  Same arrays as the stages above (k_he_*,
+// k_sync_data, k_reuse_*, k_tile_order, k_tri_*, k_edge_*, k_csr_*) by the same per-element rules -- the shared functions
+// those kernels call (tri_side, edge_alpha, data_term, reuse_tile, morton_key, edge_bucket_of, edge_record, inc_entry,
+// inc_word, inc_other_end, ipos_index) -- but another traversal: loops over one workgroup, operands in registers across
+// phases, counters, offsets and gather tables in LDS, __syncthreads() between the phases.
+// tests/test_gpu_plan_device.py compares the two paths array for array.
 // ------------------------------------------------------------------------------------------
 constexpr int kMiniV = 2048;          // vertices
 constexpr int kMiniT = 4096;          // triangles (3T half edges <= 12288)
@@ -2122,11 +2121,11 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
   for (int i = 0; i < kTri; ++i) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const int32_t u = tv[i][c], w = tv[i][c == 2 ? 0 : c + 1];
+      int32_t lo, hi;
       tr[i][c] = -1;
       if (tid + i * NT >= a.T) continue;
-      if (u < 0 || w < 0 || u >= V || w >= V || u == w) { atomicOr(&a.dflags[2], 2); continue; }  // = half_edge()
-      tr[i][c] = atomicAdd(&s_a[min(u, w)], 1);
+      if (!tri_side(tv[i][c], tv[i][c == 2 ? 0 : c + 1], V, &lo, &hi)) { atomicOr(&a.dflags[kUserChainFlags], kPlanBadIndex); continue; }
+      tr[i][c] = atomicAdd(&s_a[lo], 1);
     }
   }
   __syncthreads();
@@ -2137,8 +2136,9 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
   for (int i = 0; i < kTri; ++i) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const int32_t u = tv[i][c], w = tv[i][c == 2 ? 0 : c + 1];
-      if (tr[i][c] >= 0) s_buf[s_a[min(u, w)] + tr[i][c]] = (uint32_t)max(u, w);
+      int32_t lo, hi;
+      (void)tri_side(tv[i][c], tv[i][c == 2 ? 0 : c + 1], V, &lo, &hi);
+      if (tr[i][c] >= 0) s_buf[s_a[lo] + tr[i][c]] = (uint32_t)hi;
     }
   }
   __syncthreads();
@@ -2152,7 +2152,7 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
   MINI_STAMP(7);
   const int32_t E = mini_scan(s_b, V + 1, s_sc);
   MINI_STAMP(8);
-  if (tid == 0) a.dflags[1] = E;
+  if (tid == 0) a.dflags[kUserEdgeCount] = E;
   if (E != a.E_expect || E > kMiniE) {  // (uniform) the host's prediction was wrong: it builds again
     mini_leave_empty_plan(a, false);
     return;
@@ -2168,31 +2168,23 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
       const float2 pj = s_pos[j];
       const float dx = pi.x - pj.x, dy = pi.y - pj.y;
       a.edges[idx] = make_int2(v, j);
-      const float al = 1.0f / sqrtf(dx * dx + dy * dy);  // -ffp-contract=off: two roundings, as the oracle
+      const float al = edge_alpha(dx, dy);
       a.alpha[idx] = al;
-      if (!isfinite(al)) atomicOr(&a.dflags[0], 1);
+      if (!isfinite(al)) atomicOr(&a.dflags[kUserNonFinite], kUserNonFiniteBit);
       ++idx;
     }
   }
   MINI_STAMP(9);
   // ---- data terms (k_sync_data) ----
   for (int v = tid; v < V; v += NT) {
-    const float zi = a.mu[v] / a.scale;
-    const float wi = a.adaptive ? 1.0f / a.var[v] : 1.0f;
-    const float xi = (a.init_pred && a.pred && isfinite(a.pred[v])) ? a.pred[v] / a.scale : zi;
-    a.z[v] = zi; a.wgt[v] = wi; a.x0[v] = xi;
-    if (!(isfinite(zi) && isfinite(wi) && isfinite(xi))) atomicOr(&a.dflags[0], 1);
+    const DataTerm d = data_term(a.mu[v], a.adaptive ? a.var[v] : 1.0f, (a.init_pred && a.pred) ? a.pred[v] : NAN, a.scale, a.adaptive);
+    a.z[v] = d.z; a.wgt[v] = d.wgt; a.x0[v] = d.x0;
+    if (!data_term_finite(d)) atomicOr(&a.dflags[kUserNonFinite], kUserNonFiniteBit);
   }
   MINI_STAMP(10);
   // ---- partition from the previous frame's tile map (k_reuse_assign / scatter) ----
   for (int v = tid; v < V; v += NT) {
-    const float2 q = s_pos[v];
-    int32_t t = 0;
-    for (int l = 0; l < kPyrLevels; ++l) {
-      const int32_t c = a.pyr[pyr_cell(a.gbbox, q, l)];
-      if (c > 0) { t = c - 1; break; }
-    }
-    t = max(0, min(t, ntiles - 1));
+    const int32_t t = reuse_tile(a.gbbox, a.pyr, s_pos[v], ntiles);
     a.vt[v] = t;
     a.rank[v] = atomicAdd(&s_tl[t], 1);  // (the half-edge ranks are spent)
   }
@@ -2204,9 +2196,9 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
     if (tid < ntiles) {
       const int32_t lo = s_tl[tid];
       a.tab.lo[tid] = lo; a.tab.hi[tid] = lo + c0; a.tab.leaves[tid] = 1; a.tab.first[tid] = tid;
-      if (c0 < 1 || c0 > a.cap || c0 > kMiniTileCap) atomicOr(&a.flags[0], 64);
+      if (c0 < 1 || c0 > a.cap || c0 > kMiniTileCap) atomicOr(&a.flags[0], kPlanReuseRejected);
     }
-    if (tid == 0) { a.nseg[0] = ntiles; if (total != V) atomicOr(&a.flags[0], 64); }
+    if (tid == 0) { a.nseg[0] = ntiles; if (total != V) atomicOr(&a.flags[0], kPlanReuseRejected); }
   }
   for (int v = tid; v < V; v += NT) {
     const int32_t t = a.vt[v];
@@ -2215,7 +2207,7 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
     a.seg_pos[p] = t;
   }
   __syncthreads();
-  if (__builtin_amdgcn_readfirstlane(a.flags[0]) & 64) {  // (uniform after the barrier) rejected: bisection next
+  if (__builtin_amdgcn_readfirstlane(a.flags[0]) & kPlanReuseRejected) {  // (uniform after the barrier) rejected: bisection next
     mini_leave_empty_plan(a, true);
     return;
   }
@@ -2234,9 +2226,7 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
         if (p < n) {
           const int32_t v = a.v_i2o[lo + p];
           const float2 q = s_pos[v];
-          const uint32_t qx = (uint32_t)(65535.0f * (fminf(fmaxf(q.x, mnx), mxx) - mnx) / fmaxf(mxx - mnx, 1e-20f));
-          const uint32_t qy = (uint32_t)(65535.0f * (fminf(fmaxf(q.y, mny), mxy) - mny) / fmaxf(mxy - mny, 1e-20f));
-          k = ((uint64_t)(morton_spread16(qx) | (morton_spread16(qy) << 1)) << 32) | (uint32_t)v;
+          k = morton_key(morton_code(q.x, q.y, mnx, mny, mxx, mxy), v);
         }
         mine[h] = k;
         keys[p] = k;
@@ -2275,7 +2265,7 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
       const int32_t vo = tv[i][c];
       tr[i][c] = -1;
       if (t >= a.T) continue;
-      if (vo < 0 || vo >= V) { atomicOr(&a.flags[0], 2); a.tris_int[3 * t + c] = 0; continue; }
+      if (vo < 0 || vo >= V) { atomicOr(&a.flags[0], kPlanBadIndex); a.tris_int[3 * t + c] = 0; continue; }
       const int32_t v = s_vo2i[vo];
       tv[i][c] = v;  // (internal id from here on)
       a.tris_int[3 * t + c] = v;
@@ -2314,8 +2304,8 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
     if (tid + i * NT >= E) continue;
     const int32_t si = s_vo2i[eij_o[i].x], sj = s_vo2i[eij_o[i].y];
     const int32_t ti = s_tile[si], tj = s_tile[sj];
-    const int32_t lo = s_tl[ti], n = s_tl[ti + 1] - lo;
-    eb[i] = 2 * lo + (ti == tj ? 0 : n) + (si - lo);  // = edge_bucket()
+    const int32_t lo = s_tl[ti];
+    eb[i] = edge_bucket_of(si, ti, tj, lo, s_tl[ti + 1] - lo);
     er[i] = atomicAdd(&s_a[eb[i]], 1);
     eij_o[i] = make_int2(si, sj);                      // (internal ids from here on)
   }
@@ -2350,7 +2340,7 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
       const int32_t si = s_vo2i[gij[i].x], sj = s_vo2i[gij[i].y];
       const float2 pi = s_pos[gij[i].x], pj = s_pos[gij[i].y];
       a.eij[kk] = make_int2(si, sj);
-      a.ew[kk] = make_float4(gal[i], gal[i], a.dsign * (pi.x - pj.x), a.dsign * (pi.y - pj.y));
+      a.ew[kk] = edge_record<float4>(gal[i], gal[i], a.dsign, pi.x, pi.y, pj.x, pj.y);
       int2 r;
       r.x = atomicAdd(&s_b[si], 1);
       r.y = atomicAdd(&s_b[sj], 1);
@@ -2370,8 +2360,8 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
     for (int i = 0; i < kEdg; ++i) {
       const int32_t e = tid + i * NT;
       if (e >= E) continue;
-      s_buf[s_b[eij_o[i].x] + fr[i].x] = (uint32_t)e << 1;
-      s_buf[s_b[eij_o[i].y] + fr[i].y] = ((uint32_t)e << 1) | 1u;
+      s_buf[s_b[eij_o[i].x] + fr[i].x] = inc_entry(e, 0);
+      s_buf[s_b[eij_o[i].y] + fr[i].y] = inc_entry(e, 1);
     }
   }
   __syncthreads();
@@ -2381,11 +2371,11 @@ __global__ __launch_bounds__(kMiniThreads) void k_mini_plan(MiniArgs a) {
     (void)mini_sort_row(row, d);
     for (int i = 0; i < d; ++i) {
       const uint32_t x = row[i];
-      const int32_t kk = s_eo2i[x >> 1];
-      const int2 oe = a.edges[x >> 1];
-      row[i] = (uint32_t)kk | ((x & 1u) << 31);
-      a.gadj[s_b[v] + i] = s_vo2i[(x & 1u) ? oe.x : oe.y];  // (what k_csr_rows<true> leaves for the tile passes)
-      a.ipos[2 * kk + (int32_t)(x & 1u)] = i;
+      const int32_t kk = s_eo2i[inc_entry_edge(x)];
+      const int2 oe = a.edges[inc_entry_edge(x)];
+      row[i] = inc_word(kk, inc_entry_role(x));
+      a.gadj[s_b[v] + i] = s_vo2i[inc_other_end(inc_entry_role(x), oe.x, oe.y)];
+      a.ipos[ipos_index(kk, inc_entry_role(x))] = i;
     }
   }
   __syncthreads();
@@ -2497,7 +2487,6 @@ hipError_t DevPlanner::wait_maps() {
 
 hipError_t DevPlanner::reserve(int32_t V, int32_t E, int32_t T, int ntiles) {
   HIPRET(wait_maps());  // (buffers may be re-allocated or rewritten from here on)
-  const int64_t nk = std::max<int64_t>(std::max<int64_t>(V, 2 * (int64_t)E), 3 * (int64_t)T);
   if (V > capV_ || E > capE_ || T > capT_) {
     const int64_t v = std::max<int64_t>(V + V / 4, capV_), e = std::max<int64_t>(E + E / 4, capE_),
                   t = std::max<int64_t>(T + T / 4, capT_);
@@ -2523,7 +2512,6 @@ hipError_t DevPlanner::reserve(int32_t V, int32_t E, int32_t T, int ntiles) {
     HIPRET(rocprim::exclusive_scan(nullptr, b, counts_, counts_, (int32_t)0, (size_t)(2 * (int)v + 2), rocprim::plus<int32_t>(), nullptr)); need = std::max(need, b);  // (edge buckets: 2V + 1)
     if (need > cub_bytes_) { HIPRET(dalloc(reinterpret_cast<char**>(&cub_tmp_), need)); cub_bytes_ = need; }
   }
-  (void)nk;
   if (V > capV2_) {
     const int64_t v = std::max<int64_t>(V + V / 4, 64);
     HIPRET(dalloc(&tcnt_, 2 * (size_t)v + 2));
@@ -2579,122 +2567,169 @@ hipError_t DevPlanner::reserve(int32_t V, int32_t E, int32_t T, int ntiles) {
   return hipSuccess;
 }
 
-hipError_t DevPlanner::build(hipStream_t s, const PlanOptions& opt, int32_t V, int32_t E, int32_t T, int ntiles,
-                             int depth, const DevPlanInputs& in, DevPlanArrays* A, AllocTilesFn alloc_tiles,
-                             void* alloc_ctx, std::vector<TileDesc>* tiles_host, bool* ok, bool* index_error,
-                             const int32_t* user_flags_dev, int32_t* user_flags_host,
-                             const std::function<hipError_t()>& after_partition) {
-  *ok = false;
-  *index_error = false;
-  // option "plan_timing" (diagnostic; PlanOptions::timing): 1 synchronise after every stage and print its wall time; 2 host
-  // enqueue time only; 3 device time of the build beside its host wall time; 4 / 5 the in-kernel stamps of k_mini_plan / of tile 0
-  const int tlevel = opt.timing;
-  const bool timing = tlevel > 0;
-  auto tprev = std::chrono::steady_clock::now();
-  const bool timing_nosync = tlevel >= 2;  // host enqueue time only
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    if (!timing_nosync) (void)hipStreamSynchronize(s);
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[plan_dev] %-14s %7.3f ms\n", what, std::chrono::duration<double, std::milli>(now - tprev).count());
+namespace {
+// option "plan_timing" (diagnostic; PlanOptions::timing): 1 synchronise after every stage and print its wall time; 2 host
+// enqueue time only; 3 device time of the build beside its host wall time; 4 / 5 the in-kernel stamps of k_mini_plan / of tile 0
+struct PlanTimer {
+  using Clock = std::chrono::steady_clock;
+  const int level;
+  const hipStream_t s;
+  Clock::time_point tprev = Clock::now(), t_build0, t_enq;
+  static hipEvent_t* events() { static hipEvent_t tev[2] = {nullptr, nullptr}; return tev; }
+  static double ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+  void lap(const char* what) {
+    if (level <= 0) return;
+    if (level < 2) (void)hipStreamSynchronize(s);
+    const auto now = Clock::now();
+    std::fprintf(stderr, "[plan_dev] %-14s %7.3f ms\n", what, ms(tprev, now));
     tprev = now;
-  };
-  HIPRET(reserve(V, E, T, ntiles));
-  lap("reserve");
-  const bool timing_dev = tlevel == 3;  // device time of the build's launches (events on `s`) beside its host wall time
-  static hipEvent_t tev[2] = {nullptr, nullptr};
-  const auto t_build0 = std::chrono::steady_clock::now();
-  if (timing_dev) {
-    if (!tev[0]) { (void)hipEventCreate(&tev[0]); (void)hipEventCreate(&tev[1]); }
-    (void)hipEventRecord(tev[0], s);
   }
-  const size_t lds1 = ((size_t)(V + 31) / 32) * 4 + kCapExt * 4 + kHash * 8;
-  const size_t lds2 = lds1 + (size_t)kBucketInts * 4;  // + the bucket counts / offsets of the local edge list
-  if (!attr_set_) {  // per planner (= per handle = per device), not per process
-    HIPRET(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_pass1), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-    HIPRET(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_pass2), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-    HIPRET(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_fused), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-    HIPRET(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mini_plan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMiniLds));
-    attr_set_ = true;
+  void begin() {  // behind reserve(): the build's launches start here
+    t_build0 = Clock::now();
+    if (level != 3) return;
+    if (!events()[0]) { (void)hipEventCreate(&events()[0]); (void)hipEventCreate(&events()[1]); }
+    (void)hipEventRecord(events()[0], s);
   }
-  // segment tables
-  int32_t* st = seg_tab_;
-  SegTab tab[2] = {{st, st + kSegCap, st + 2 * kSegCap, st + 3 * kSegCap},
-                   {st + 4 * kSegCap, st + 5 * kSegCap, st + 6 * kSegCap, st + 7 * kSegCap}};
-  uint32_t* bbox = reinterpret_cast<uint32_t*>(st + 8 * kSegCap);  // 4 * kSegCap
-  int32_t* mid_raw[2] = {st + 12 * kSegCap, st + 13 * kSegCap};
-  int32_t* child_base = st + 14 * kSegCap;
-  int32_t* mid_out = st + 15 * kSegCap;
-  int32_t* nseg = st + 16 * kSegCap;  // [2]
-  int32_t* perm = A->v_i2o;
-  const bool weighted = weight_mode_ != 0;
-  const int vb = bits_for(V);
-  // flags; the vertex order outputs (every entry is an index for the later stages, whatever the
-  // partition); the triangle stage's counts and cursors
-  const bool reuse = reuse_next_;  // the caller asked for the previous frame's partition (map_usable())
-  // small frame of a graph sync: stages A-E (and the edge derivation + data terms in front of them)
-  // in one launch of one workgroup (k_mini_plan)
-  const bool mini = mini_set_ && reuse && mini_eligible(V, T, E) && ntiles <= kSegCap && expect_E_ == E;
-  mini_used_ = mini_used_ || mini;  // (sticky until the next offer: a retry after a rejected partition keeps
-  mini_set_ = false;                //  what the mini launch derived -- edges and data terms come first in it)
-  // (the reuse path's tile counters and stage C's bucket counts ride along: their scratch is free from
-  // the start there, while the bisection stages still use it)
-  int32_t* ecnt0 = reinterpret_cast<int32_t*>(keys_b_);
-  if (!mini) zero4(s, flags_, 8, A->v_o2i, V, tile_of_int_, V, reuse ? reuse_cnt_ : nullptr, (int64_t)kCntStride * ntiles,
-        (reuse && E > 0) ? ecnt0 : nullptr, 2 * (int64_t)V + 1);
-  reuse_next_ = false;
-  last_reused_ = false;
-  if (weight_mode_ == 2 && !reuse)  // (mode 1: w_int_ already holds the weights, see weights_from_tiles / _scale_)
-    hipLaunchKernelGGL(k_weights_from_grid, grid1(V), dim3(256), 0, s, V, in.pos, grid_bounds_, grid_w_, w_int_);
-
-  // ---- stage A ----
-  int cur = 0;
-  if (mini) {
-    MiniArgs a;
-    a.V = V; a.T = T; a.E_expect = E; a.ntiles = ntiles;
-    a.cap = (int32_t)std::min<int64_t>(kOrderCap, ((int64_t)V * 3) / ntiles + 16);
-    a.tris = mini_.tris ? mini_.tris : in.tris; a.pos = mini_.pos ? mini_.pos : in.pos; a.pos_out = const_cast<float2*>(in.pos);
-    a.tris_out = const_cast<int32_t*>(in.tris);
-    a.mu = mini_.mu; a.var = mini_.var; a.pred = mini_.pred;
-    a.scale = mini_.scale; a.adaptive = mini_.adaptive; a.init_pred = mini_.init_pred;
-    a.dsign = opt.d_sign < 0 ? -1.0f : 1.0f;
-    a.edges = mini_.edges; a.alpha = mini_.alpha; a.z = mini_.z; a.wgt = mini_.wgt; a.x0 = mini_.x0;
-    a.dflags = mini_.dflags;
-    a.rank = rank_;
-    a.vt = w_int_;
-    a.gbbox = gbbox_; a.pyr = cell_pyr_; a.tab = tab[0]; a.nseg = nseg; a.flags = flags_;
-    a.seg_pos = seg_pos_;
-    a.v_i2o = A->v_i2o; a.v_o2i = A->v_o2i; a.tile_of_int = tile_of_int_;
-    a.tris_int = A->tris; a.trow = A->trow; a.tinc = reinterpret_cast<uint32_t*>(A->tinc);
-    a.e_i2o = A->e_i2o; a.e_o2i = A->e_o2i; a.eij = A->eij; a.ew = A->ew; a.estart = estart_;
-    a.grow = A->grow; a.ginc = reinterpret_cast<uint32_t*>(A->ginc); a.gadj = gadj_; a.ipos = ipos_;
-    const bool mini_prof = tlevel == 4;
-    a.prof = mini_prof ? reinterpret_cast<long long*>(wscan_) : nullptr;  // (free in this path)
-    hipLaunchKernelGGL(k_mini_plan, dim3(1), dim3(kMiniThreads), kMiniLds, s, a);
-    if (mini_prof) {
-      long long h[20] = {0};
-      (void)hipStreamSynchronize(s);
-      (void)hipMemcpy(h, wscan_, sizeof(h), hipMemcpyDeviceToHost);
+  void enqueued() {  // the last launch in front of the build's synchronisation is out
+    if (level == 3) (void)hipEventRecord(events()[1], s);
+    t_enq = Clock::now();
+  }
+  void synchronised() {
+    if (level != 3) return;
+    float dev_ms = 0.f;
+    (void)hipEventElapsedTime(&dev_ms, events()[0], events()[1]);
+    std::fprintf(stderr, "[plan_dev] device %.3f ms; host: enqueued after %.3f ms, synchronised after %.3f ms\n", dev_ms,
+                 ms(t_build0, t_enq), ms(t_build0, Clock::now()));
+  }
+  // levels 4 / 5: the kernel's stamps land in `scratch` (its argument; null at every other level) and are printed behind it
+  long long* stamps(int at_level, long long* scratch) const { return level == at_level ? scratch : nullptr; }
+  void print_stamps(int at_level, const long long* scratch) {
+    if (level != at_level) return;
+    long long h[20] = {0};
+    (void)hipStreamSynchronize(s);
+    (void)hipMemcpy(h, scratch, at_level == 4 ? sizeof(h) : 10 * sizeof(h[0]), hipMemcpyDeviceToHost);
+    if (at_level == 4) {
       std::fprintf(stderr, "[mini] ticks per phase:");
       int last = 1;
       for (int q = 2; q < 20 && h[q]; ++q) { std::fprintf(stderr, " %lld", h[q] - h[q - 1]); last = q; }
       std::fprintf(stderr, "  total %lld\n", h[last] - h[1]);
+    } else {
+      std::fprintf(stderr, "[tile0] ticks: rings %lld hash %lld keys %lld lookback %lld sort %lld slot rows %lld records %lld  total %lld\n",
+                   h[2] - h[1], h[3] - h[2], h[4] - h[3], h[5] - h[4], h[6] - h[5], h[7] - h[6], h[8] - h[7], h[8] - h[1]);
     }
-    last_reused_ = true;
-  } else if (reuse) {
-    // partition from the previous frame's tile map: lookup + counts, ranges, counting scatter
-    int32_t* tile_cnt = reuse_cnt_;          // one counter per cache line
-    int32_t* vt = w_int_;                    // (no weights in this path)
-    int32_t* vrank = reinterpret_cast<int32_t*>(wscan_);  // (the weight scratch of the bisection path)
-    hipLaunchKernelGGL(k_reuse_assign, grid1(V), dim3(256), 0, s, V, ntiles, in.pos, gbbox_, cell_pyr_, vt, vrank, tile_cnt);
-    // (cost-balanced partitions hold 0.5..1.8 x the mean on purpose; a tile that is too LARGE for LDS or
-    // a kernel configuration is found by the fit check of the caller like on any other partition)
-    const int32_t cap = (int32_t)std::min<int64_t>(kOrderCap, ((int64_t)V * 3) / ntiles + 16);
-    hipLaunchKernelGGL(k_reuse_scatter, grid1(V), dim3(256), 0, s, V, ntiles, cap, vt, vrank, tile_cnt, tab[0], nseg, flags_,
-                       perm, seg_pos_);
-    last_reused_ = true;
-  } else {
-  int levels = 0;
+  }
+};
+}  // namespace
+
+// What the stages of one build share: the call, the kind of build, the segment tables and -- in ONE place -- what each scratch
+// buffer holds at which stage.  Filled by DevPlanner::build(); the partition stages advance `cur`.
+struct DevPlanner::Build {
+  DevPlanner& p;
+  hipStream_t s; const PlanOptions& opt; int32_t V, E, T; int ntiles, depth; const DevPlanInputs& in; DevPlanArrays* A;  // the call
+  AllocTilesFn alloc_tiles; void* alloc_ctx;
+  const int32_t* user_dev;  // the caller's words, or null
+  bool reuse;               // partition from the previous frame's tile map (the caller asked: map_usable())
+  bool mini;                // ... and everything in front of the tile passes in one launch (k_mini_plan)
+  bool weighted;            // bisection on the integer cost weights in w_int_
+  long long *mini_prof, *tile_prof;  // plan_timing 4 / 5: where the kernels leave their stamps, else null
+  bool tri_stage = false, spec = false, fused = false, tiles_built = false;
+  size_t lds1 = ((size_t)(V + 31) / 32) * 4 + kCapExt * 4 + kHash * 8;  // dynamic LDS of tile pass 1
+  size_t lds2 = lds1 + (size_t)kBucketInts * 4;  // ... of pass 2 and the fused pass: + the bucket counts / offsets of the local edge list
+  // seg_tab_: 2 tables x 4 arrays, bbox (4), mid_raw x 2, child_base, mid_out, nseg x 2 (+ pad), axis
+  int32_t* st = p.seg_tab_;
+  SegTab tab[2] = {{st, st + kSegCap, st + 2 * kSegCap, st + 3 * kSegCap},
+                   {st + 4 * kSegCap, st + 5 * kSegCap, st + 6 * kSegCap, st + 7 * kSegCap}};
+  uint32_t* bbox = reinterpret_cast<uint32_t*>(st + 8 * kSegCap);  // 4 * kSegCap
+  int32_t *mid_raw[2] = {st + 12 * kSegCap, st + 13 * kSegCap}, *child_base = st + 14 * kSegCap, *mid_out = st + 15 * kSegCap;
+  int32_t *nseg = st + 16 * kSegCap /* [2] */, *axis = st + 16 * kSegCap + 16;
+  int cur = 0;               // the table the last partition step wrote
+  SegTab leaf{};             // = tab[cur] once the partition stands: lo = vstart, hi = vstart + n_own per tile
+  int32_t* perm = A->v_i2o;  // the vertex ids in segment order (stage A), then in tile order (stage B)
+  // ---- scratch aliases: a buffer serves several stages in turn; no two uses below overlap in time ----
+  // keys_a_  bisection: keys of the x entry sort, in | out.  Stage C: the edge ids in bucket order.
+  uint32_t *key_in = reinterpret_cast<uint32_t*>(p.keys_a_), *key_out = key_in + p.capV_, *esorted = key_in;
+  // keys_b_  bisection: values of the x entry sort | posx (place of a vertex in the x list, for the subtrees).  Stage C: the
+  //          2V + 1 bucket counts -- zeroed by the build's first launch on the reuse path, where the buffer is free from the
+  //          start, and behind the bisection otherwise.
+  uint32_t *val_in = reinterpret_cast<uint32_t*>(p.keys_b_), *posx = val_in + p.capV_;
+  int32_t* ecnt = reinterpret_cast<int32_t*>(p.keys_b_);
+  // vals_a_ / vals_b_  bisection: the ids sorted along x / along y, double-buffered.  Stage C: vals_b_ = the bucket offsets
+  //          (the lists are dead by then).
+  uint32_t *LX[2] = {p.vals_a_, p.vals_a_ + p.capV_}, *LY[2] = {p.vals_b_, p.vals_b_ + p.capV_};
+  int32_t* eoff = reinterpret_cast<int32_t*>(p.vals_b_);
+  // wsort_ / wscan_  bisection: first keys (in | out) / values of the y entry sort on the second stream, then per level the
+  //          weights or side flags along the chosen axis / their inclusive scan.  Reuse: wscan_ = the rank of a vertex inside
+  //          its tile.  plan_timing 4 / 5: wscan_ = the kernels' stamps (free in those paths).
+  uint32_t *key_in2 = reinterpret_cast<uint32_t*>(p.wsort_), *key_out2 = key_in2 + p.capV_, *val_in2 = reinterpret_cast<uint32_t*>(p.wscan_);
+  int32_t* vrank = reinterpret_cast<int32_t*>(p.wscan_);
+  int32_t* vt = p.w_int_;    // w_int_  bisection: the cost weights by original id.  Reuse / one launch: the tile of a vertex.
+  int32_t* side = p.counts_; // counts_  bisection: a vertex's side at this level.  Stage D: degree counts (zeroed by k_edge_count).
+  // rank_    [0, 2E): stage C one rank per edge, then stage D one per edge END (int2 per edge, k_edge_rows_gather);
+  //          [2 capE_, ..): rank_tri_, the triangle stages' ranks (they run beside C and D on the second stream).
+  int2* rank2 = reinterpret_cast<int2*>(p.rank_);
+  // hpin_    page-locked landing area of k_publish: the flag word and totals | the caller's words | the descriptors
+  int32_t *hflags = reinterpret_cast<int32_t*>(p.hpin_), *huser = reinterpret_cast<int32_t*>(p.hpin_ + 64);
+  TileDesc* htiles = reinterpret_cast<TileDesc*>(p.hpin_ + 256);
+
+  TileGraph graph() const {
+    TileGraph G;
+    G.V = V; G.depth = depth; G.grow = A->grow; G.ginc = A->ginc; G.eij = A->eij; G.e_i2o = A->e_i2o; G.e_o2i = A->e_o2i;
+    G.gadj = p.gadj_; G.ipos = p.ipos_;
+    return G;
+  }
+  TileOut tile_out() const {  // (at launch time: alloc_tiles() sets the tile arrays of *A)
+    TileOut O;
+    O.ew = A->ew; O.tiles = A->tiles; O.t_vmap = A->t_vmap; O.t_emap = A->t_emap; O.t_eij = A->t_eij; O.t_ew = A->t_ew;
+    O.t_srow = A->t_srow; O.flags = p.flags_; O.lane_order = opt.lane_order == 2 ? 1 : 0; O.prof = tile_prof;
+    return O;
+  }
+};
+
+// (cost-balanced partitions hold 0.5..1.8 x the mean on purpose; a tile that is too LARGE for LDS or a kernel configuration is
+// found by the fit check of the caller like on any other partition)
+static int32_t reuse_tile_cap(int32_t V, int ntiles) { return (int32_t)std::min<int64_t>(kOrderCap, ((int64_t)V * 3) / ntiles + 16); }
+
+// ---- stage A, small frame of a graph sync: stages A-E (and the edge derivation + data terms in front of them) in one launch
+// of one workgroup ----
+void DevPlanner::partition_mini(Build& B) {
+  DevPlanArrays* A = B.A;
+  MiniArgs a;
+  a.V = B.V; a.T = B.T; a.E_expect = B.E; a.ntiles = B.ntiles; a.cap = reuse_tile_cap(B.V, B.ntiles);
+  a.tris = mini_.tris ? mini_.tris : B.in.tris; a.pos = mini_.pos ? mini_.pos : B.in.pos;
+  a.pos_out = const_cast<float2*>(B.in.pos); a.tris_out = const_cast<int32_t*>(B.in.tris);
+  a.mu = mini_.mu; a.var = mini_.var; a.pred = mini_.pred; a.scale = mini_.scale; a.adaptive = mini_.adaptive; a.init_pred = mini_.init_pred;
+  a.dsign = edge_dsign(B.opt.d_sign);
+  a.edges = mini_.edges; a.alpha = mini_.alpha; a.z = mini_.z; a.wgt = mini_.wgt; a.x0 = mini_.x0; a.dflags = mini_.dflags;
+  a.rank = rank_; a.vt = B.vt; a.seg_pos = seg_pos_;
+  a.gbbox = gbbox_; a.pyr = cell_pyr_; a.tab = B.tab[0]; a.nseg = B.nseg; a.flags = flags_;
+  a.v_i2o = A->v_i2o; a.v_o2i = A->v_o2i; a.tile_of_int = tile_of_int_;
+  a.tris_int = A->tris; a.trow = A->trow; a.tinc = reinterpret_cast<uint32_t*>(A->tinc);
+  a.e_i2o = A->e_i2o; a.e_o2i = A->e_o2i; a.eij = A->eij; a.ew = A->ew; a.estart = estart_;
+  a.grow = A->grow; a.ginc = reinterpret_cast<uint32_t*>(A->ginc); a.gadj = gadj_; a.ipos = ipos_; a.prof = B.mini_prof;
+  hipLaunchKernelGGL(k_mini_plan, dim3(1), dim3(kMiniThreads), kMiniLds, B.s, a);
+  last_reused_ = true;
+}
+
+// ---- stage A, frame stream: the partition from the previous frame's tile map: lookup + counts, ranges, counting scatter
+// (which writes the table of a finished bisection by construction: no k_rcb_check) ----
+void DevPlanner::partition_reuse(Build& B) {
+  int32_t* tile_cnt = reuse_cnt_;  // one counter per cache line
+  hipLaunchKernelGGL(k_reuse_assign, grid1(B.V), dim3(256), 0, B.s, B.V, B.ntiles, B.in.pos, gbbox_, cell_pyr_, B.vt, B.vrank, tile_cnt);
+  hipLaunchKernelGGL(k_reuse_scatter, grid1(B.V), dim3(256), 0, B.s, B.V, B.ntiles, reuse_tile_cap(B.V, B.ntiles), B.vt, B.vrank,
+                     tile_cnt, B.tab[0], B.nseg, flags_, B.perm, seg_pos_);
+  last_reused_ = true;
+}
+
+// ---- stage A: exact bisection, one round of kernels per level, the deep levels by one workgroup per subtree ----
+hipError_t DevPlanner::partition_bisect(Build& B) {
+  const hipStream_t s = B.s;
+  const int32_t V = B.V, ntiles = B.ntiles;
+  const DevPlanInputs& in = B.in;
+  const bool weighted = B.weighted;
+  SegTab* tab = B.tab;
+  uint32_t **LX = B.LX, **LY = B.LY;
+  int32_t *nseg = B.nseg, *axis = B.axis, *side = B.side, *perm = B.perm;
+  int cur = 0, levels = 0;
   while ((1 << levels) < ntiles) ++levels;
   // deep levels in LDS: from the first level whose segments hold <= kSubCap vertices (1.5 x margin
   // for uneven weighted splits) and <= kSubLeaves tiles
@@ -2706,31 +2741,19 @@ hipError_t DevPlanner::build(hipStream_t s, const PlanOptions& opt, int32_t V, i
         break;
       }
   const bool lists = sub_level > 0;  // (a lone subtree sorts itself, on the coordinates)
-  // the two sorted lists, double-buffered; scratch of the two entry sorts
-  uint32_t* LX[2] = {vals_a_, vals_a_ + capV_};
-  uint32_t* LY[2] = {vals_b_, vals_b_ + capV_};
-  uint32_t* key_in = reinterpret_cast<uint32_t*>(keys_a_);
-  uint32_t* key_out = reinterpret_cast<uint32_t*>(keys_a_) + capV_;
-  uint32_t* val_in = reinterpret_cast<uint32_t*>(keys_b_);
-  uint32_t* posx = reinterpret_cast<uint32_t*>(keys_b_) + capV_;
-  int32_t* side = counts_;
-  int32_t* axis = st + 16 * kSegCap + 16;
   if (lists) {  // ids sorted along x (this stream) and along y (second stream): (coordinate, id)
     HIPRET(hipEventRecord(ev_fork_, s));
     HIPRET(hipStreamWaitEvent(s2_, ev_fork_, 0));
-    hipLaunchKernelGGL(k_rank_keys, grid1(V), dim3(256), 0, s, V, in.pos, 0, key_in, val_in);
+    hipLaunchKernelGGL(k_rank_keys, grid1(V), dim3(256), 0, s, V, in.pos, 0, B.key_in, B.val_in);
     size_t tb2 = cub_bytes_;
-    HIPRET(rocprim::radix_sort_pairs(cub_tmp_, tb2, key_in, key_out, val_in, LX[0], V, 0, 32, s));
-    uint32_t* key_in2 = reinterpret_cast<uint32_t*>(wsort_);  // (the weight scratch is not in use yet)
-    uint32_t* key_out2 = reinterpret_cast<uint32_t*>(wsort_) + capV_;
-    uint32_t* val_in2 = reinterpret_cast<uint32_t*>(wscan_);
-    hipLaunchKernelGGL(k_rank_keys, grid1(V), dim3(256), 0, s2_, V, in.pos, 1, key_in2, val_in2);
+    HIPRET(rocprim::radix_sort_pairs(cub_tmp_, tb2, B.key_in, B.key_out, B.val_in, LX[0], V, 0, 32, s));
+    hipLaunchKernelGGL(k_rank_keys, grid1(V), dim3(256), 0, s2_, V, in.pos, 1, B.key_in2, B.val_in2);
     size_t tb3 = tcub_bytes_;
-    HIPRET(rocprim::radix_sort_pairs(tcub_tmp_, tb3, key_in2, key_out2, val_in2, LY[0], V, 0, 32, s2_));
+    HIPRET(rocprim::radix_sort_pairs(tcub_tmp_, tb3, B.key_in2, B.key_out2, B.val_in2, LY[0], V, 0, 32, s2_));
     HIPRET(hipEventRecord(ev_join_, s2_));
     HIPRET(hipStreamWaitEvent(s, ev_join_, 0));
   }
-  hipLaunchKernelGGL(k_rcb_init, grid1(V), dim3(256), 0, s, V, ntiles, perm, seg_pos_, tab[0], nseg, bbox, mid_raw[0]);
+  hipLaunchKernelGGL(k_rcb_init, grid1(V), dim3(256), 0, s, V, ntiles, perm, seg_pos_, tab[0], nseg, B.bbox, B.mid_raw[0]);
   int lb = 0;
   for (int lev = 0; lev < sub_level; ++lev, cur ^= 1, lb ^= 1) {
     hipLaunchKernelGGL(k_lvl_axis, dim3((unsigned)(((1 << lev) + 255) / 256)), dim3(256), 0, s, nseg + cur, tab[cur], LX[lb], LY[lb],
@@ -2748,11 +2771,11 @@ hipError_t DevPlanner::build(hipStream_t s, const PlanOptions& opt, int32_t V, i
         size_t tb = cub_bytes_;
         HIPRET(rocprim::inclusive_scan(cub_tmp_, tb, wsort_, wscan_, (size_t)(V), rocprim::plus<int32_t>(), s));
       }
-      hipLaunchKernelGGL(k_rcb_mid, grid1(V), dim3(256), 0, s, V, seg_pos_, tab[cur], wsort_, wscan_, mid_raw[cur]);
+      hipLaunchKernelGGL(k_rcb_mid, grid1(V), dim3(256), 0, s, V, seg_pos_, tab[cur], wsort_, wscan_, B.mid_raw[cur]);
     }
     hipLaunchKernelGGL(k_rcb_split, dim3(1), dim3(kSegCap), 0, s, nseg + cur, nseg + (cur ^ 1), tab[cur], tab[cur ^ 1],
-                       mid_raw[cur], mid_raw[cur ^ 1], weighted ? 1 : 0, child_base, mid_out, bbox);
-    hipLaunchKernelGGL(k_lvl_side, grid1(V), dim3(256), 0, s, V, seg_pos_, axis, tab[cur].leaves, mid_out, LX[lb], LY[lb], side);
+                       B.mid_raw[cur], B.mid_raw[cur ^ 1], weighted ? 1 : 0, B.child_base, B.mid_out, B.bbox);
+    hipLaunchKernelGGL(k_lvl_side, grid1(V), dim3(256), 0, s, V, seg_pos_, axis, tab[cur].leaves, B.mid_out, LX[lb], LY[lb], side);
     if (one_launch_scans) {  // side flags + inclusive scan in one launch
       ScanState st;
       HIPRET(scan_state(s, scan_agg_[0], scan_flag_[0], &scan_epoch_[0], flags_, &st));
@@ -2763,206 +2786,235 @@ hipError_t DevPlanner::build(hipStream_t s, const PlanOptions& opt, int32_t V, i
       size_t tb = cub_bytes_;
       HIPRET(rocprim::inclusive_scan(cub_tmp_, tb, wsort_, wscan_, (size_t)(V), rocprim::plus<int32_t>(), s));
     }
-    hipLaunchKernelGGL(k_lvl_scatter, grid1(V), dim3(256), 0, s, V, seg_pos_, tab[cur], mid_out, child_base, wsort_, wscan_,
+    hipLaunchKernelGGL(k_lvl_scatter, grid1(V), dim3(256), 0, s, V, seg_pos_, tab[cur], B.mid_out, B.child_base, wsort_, wscan_,
                        LX[lb], LY[lb], LX[lb ^ 1], LY[lb ^ 1]);
   }
   // perm = the x list (any order inside a segment serves the later stages); posx for the subtrees
-  if (lists) hipLaunchKernelGGL(k_lvl_posx, grid1(V), dim3(256), 0, s, V, LX[lb], posx, perm);
-  if (sub_level < levels) {
-    const size_t lds_sub = kSubLdsBytes;
+  if (lists) hipLaunchKernelGGL(k_lvl_posx, grid1(V), dim3(256), 0, s, V, LX[lb], B.posx, perm);
+  if (sub_level < levels) {  // the subtree hand-over
     if (!sub_attr_set_) {
       HIPRET(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rcb_subtree), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds_sub));
+                                 (int)kSubLdsBytes));
       sub_attr_set_ = true;
     }
-    if (sub_level == 0) hipLaunchKernelGGL(k_rcb_bbox, dim3(1), dim3(1024), 0, s, nseg + cur, tab[cur], perm, in.pos, bbox);
-    if (sub_level == 0) hipLaunchKernelGGL(k_save_gbbox, dim3(1), dim3(64), 0, s, bbox, gbbox_);
-    hipLaunchKernelGGL(k_rcb_subtree, dim3(1 << sub_level), dim3(kSubThreads), lds_sub, s, nseg + cur, tab[cur], tab[cur ^ 1],
-                       nseg + (cur ^ 1), ntiles, perm, seg_pos_, in.pos, LX[lb], LY[lb], posx, w_int_, weighted ? 1 : 0, vb,
-                       lists ? 0 : 1, (opt.debug_sub_cap > 0 && sub_extra_levels_ == 0) ? std::min(opt.debug_sub_cap, kSubCap) : kSubCap,
-                       flags_);
+    if (sub_level == 0) hipLaunchKernelGGL(k_rcb_bbox, dim3(1), dim3(1024), 0, s, nseg + cur, tab[cur], perm, in.pos, B.bbox);
+    if (sub_level == 0) hipLaunchKernelGGL(k_save_gbbox, dim3(1), dim3(64), 0, s, B.bbox, gbbox_);
+    hipLaunchKernelGGL(k_rcb_subtree, dim3(1 << sub_level), dim3(kSubThreads), kSubLdsBytes, s, nseg + cur, tab[cur], tab[cur ^ 1],
+                       nseg + (cur ^ 1), ntiles, perm, seg_pos_, in.pos, LX[lb], LY[lb], B.posx, w_int_, weighted ? 1 : 0, bits_for(V),
+                       lists ? 0 : 1,
+                       (B.opt.debug_sub_cap > 0 && sub_extra_levels_ == 0) ? std::min(B.opt.debug_sub_cap, kSubCap) : kSubCap, flags_);
     cur ^= 1;
   }
-  }  // (exact bisection)
-  if (!reuse)  // (the reuse path writes the table of a finished bisection by construction)
-    hipLaunchKernelGGL(k_rcb_check, dim3(1), dim3(kSegCap), 0, s, nseg + cur, tab[cur], ntiles, flags_);
-  const SegTab leaf = tab[cur];  // lo = vstart, hi = vstart + n_own per tile
-  lap("A rcb");
+  hipLaunchKernelGGL(k_rcb_check, dim3(1), dim3(kSegCap), 0, s, nseg + cur, tab[cur], ntiles, flags_);
+  B.cur = cur;
+  return hipSuccess;
+}
 
-  // ---- stage B ----
-  if (!mini)
-    hipLaunchKernelGGL(k_tile_order, dim3((unsigned)ntiles), dim3(256), 0, s, V, ntiles, leaf.lo, leaf.hi, in.pos, gbbox_, perm,
-                       A->v_o2i, tile_of_int_, flags_);
+// ---- stage B: vertex order inside the tiles ----
+void DevPlanner::order_vertices(Build& B) {
+  hipLaunchKernelGGL(k_tile_order, dim3((unsigned)B.ntiles), dim3(256), 0, B.s, B.V, B.ntiles, B.leaf.lo, B.leaf.hi, B.in.pos, gbbox_,
+                     B.perm, B.A->v_o2i, tile_of_int_, flags_);
+}
 
-  lap("B morton");
-  if (after_partition) HIPRET(after_partition());  // the caller's edge / data arrays arrive now
-  // ---- stage E: vertex -> triangle CSR; needs only the vertex order, so it runs beside the edge
-  // stages (C, D, tile pass 1) on a second stream and joins before the flags are read ----
-  const bool tri_stage = T > 0 && in.tris && !mini;
-  if (tri_stage) {
-    HIPRET(hipEventRecord(ev_fork_, s));
-    HIPRET(hipStreamWaitEvent(s2_, ev_fork_, 0));
-    zero4(s2_, tcnt_, (int64_t)V + 2);  // (on the second stream: not one more job of the build's first launch)
-    hipLaunchKernelGGL(k_tri_count, grid1(3 * (int64_t)T), dim3(256), 0, s2_, 3 * T, V, in.tris, A->v_o2i, A->tris, tcnt_,
-                       rank_tri_, flags_);
-    HIPRET(scan_i32(s2_, 1, tcnt_, A->trow, (int64_t)V + 1, false, tcub_tmp_, tcub_bytes_));
-    hipLaunchKernelGGL(k_tri_fill, grid1(3 * (int64_t)T), dim3(256), 0, s2_, 3 * T, V, in.tris, A->tris, A->trow, rank_tri_,
-                       reinterpret_cast<uint32_t*>(A->tinc));
-    hipLaunchKernelGGL(k_csr_rows<false>, grid1(V), dim3(256), 0, s2_, V, A->trow, nullptr,
-                       reinterpret_cast<uint32_t*>(A->tinc));
-    HIPRET(hipEventRecord(ev_join_, s2_));
-  }
-  // ---- stage C ----
-  if (mini) {
-    // (stages C and D are part of k_mini_plan)
-  } else if (E > 0) {
-    int32_t* ecnt = reinterpret_cast<int32_t*>(keys_b_);     // 2V + 1 bucket counts
-    int32_t* eoff = reinterpret_cast<int32_t*>(vals_b_);     // (the lists of stage A are dead)
-    uint32_t* esorted = reinterpret_cast<uint32_t*>(keys_a_);
-    // stage C's bucket counts (the reuse path zeroed them with its first launch); stage D's degree
-    // counts are zeroed by k_edge_count
-    if (!reuse) zero4(s, ecnt, 2 * (int64_t)V + 1);
-    hipLaunchKernelGGL(k_edge_count, grid1(std::max<int64_t>(E, (int64_t)V + 1)), dim3(256), 0, s, E, V, in.edges, A->v_o2i,
-                       tile_of_int_, leaf.lo, leaf.hi, ecnt, rank_, flags_, counts_);
-    HIPRET(scan_i32(s, 0, ecnt, eoff, 2 * (int64_t)V + 1, false, cub_tmp_, cub_bytes_));
-    hipLaunchKernelGGL(k_edge_fill, grid1(E), dim3(256), 0, s, E, V, in.edges, A->v_o2i, tile_of_int_, leaf.lo, leaf.hi, eoff,
-                       rank_, esorted);
-    // bucket sort + edge records + degree counts of stage D (kSegCap tiles <= 2V rows / 256 blocks * 256: the
-    // grid covers estart[0 .. ntiles] as long as 2V >= ntiles + 1, i.e. always: a tile owns a vertex)
-    hipLaunchKernelGGL(k_edge_rows_gather, grid1(std::max<int64_t>(2 * (int64_t)V, ntiles + 1)), dim3(256), 0, s, 2 * V, eoff,
-                       esorted, in.edges, in.alpha, in.beta, in.pos, A->v_o2i, A->e_i2o, A->e_o2i, A->eij, A->ew, V, E, ntiles,
-                       leaf.lo, estart_, opt.d_sign < 0 ? -1.0f : 1.0f, counts_, reinterpret_cast<int2*>(rank_));
-  } else {
-    HIPRET(hipMemsetAsync(estart_, 0, sizeof(int32_t) * (size_t)(ntiles + 2), s));
-  }
-  lap("C edges");
-  // ---- stage D ----
-  if (mini) {
-  } else if (E > 0) {
-    int2* rank2 = reinterpret_cast<int2*>(rank_);  // (degree counts and ranks: k_edge_rows_gather)
-    HIPRET(scan_i32(s, 0, counts_, A->grow, (int64_t)V + 1, false, cub_tmp_, cub_bytes_));
-    hipLaunchKernelGGL(k_csr_fill, grid1(E), dim3(256), 0, s, E, A->eij, A->e_o2i, A->grow, rank2,
-                       reinterpret_cast<uint32_t*>(A->ginc));
-    hipLaunchKernelGGL(k_csr_rows<true>, grid1(V), dim3(256), 0, s, V, A->grow, A->e_o2i,
-                       reinterpret_cast<uint32_t*>(A->ginc), A->eij, gadj_, ipos_);
-  } else {
-    HIPRET(hipMemsetAsync(A->grow, 0, sizeof(int32_t) * ((size_t)V + 1), s));
-  }
-  lap("D csr");
-  // ---- stage F ----
-  TileGraph G;
-  G.V = V; G.depth = depth; G.grow = A->grow; G.ginc = A->ginc; G.eij = A->eij; G.e_i2o = A->e_i2o; G.e_o2i = A->e_o2i;
-  G.gadj = gadj_; G.ipos = ipos_;
-  // The tile arrays are sized from the totals pass 1 counts.  A frame stream does not wait for them:
-  // the arrays are allocated for 9/8 of the PREVIOUS build's totals, pass 2 is launched right behind
-  // pass 1 and the one synchronisation at the end tells whether the guess held (flags bit 128: the
-  // exact sizes are known by then and pass 2 is simply run again).  First build on a handle: one more
-  // round trip, as before.
-  const bool spec = spec_nv_ > 0 && spec_tiles_ >= ntiles;
-  if (spec && alloc_tiles(alloc_ctx, (size_t)spec_tiles_, (size_t)spec_nv_, (size_t)spec_ne_, (size_t)spec_ns_) != 0)
+// ---- stage E: vertex -> triangle CSR; needs only the vertex order, so it runs beside the edge stages (C, D, tile pass 1) on
+// a second stream and joins before the flags are read ----
+hipError_t DevPlanner::triangle_csr(Build& B) {
+  const int32_t V = B.V, T = B.T;
+  DevPlanArrays* A = B.A;
+  HIPRET(hipEventRecord(ev_fork_, B.s));
+  HIPRET(hipStreamWaitEvent(s2_, ev_fork_, 0));
+  zero4(s2_, tcnt_, (int64_t)V + 2);  // (on the second stream: not one more job of the build's first launch)
+  hipLaunchKernelGGL(k_tri_count, grid1(3 * (int64_t)T), dim3(256), 0, s2_, 3 * T, V, B.in.tris, A->v_o2i, A->tris, tcnt_,
+                     rank_tri_, flags_);
+  HIPRET(scan_i32(s2_, 1, tcnt_, A->trow, (int64_t)V + 1, false, tcub_tmp_, tcub_bytes_));
+  hipLaunchKernelGGL(k_tri_fill, grid1(3 * (int64_t)T), dim3(256), 0, s2_, 3 * T, V, B.in.tris, A->tris, A->trow, rank_tri_,
+                     reinterpret_cast<uint32_t*>(A->tinc));
+  hipLaunchKernelGGL(k_csr_rows<false>, grid1(V), dim3(256), 0, s2_, V, A->trow, nullptr, reinterpret_cast<uint32_t*>(A->tinc));
+  return hipEventRecord(ev_join_, s2_);
+}
+
+// ---- stage C: edge order and edge records ----
+hipError_t DevPlanner::edge_order(Build& B) {
+  const hipStream_t s = B.s;
+  const int32_t V = B.V, E = B.E;
+  const DevPlanInputs& in = B.in;
+  DevPlanArrays* A = B.A;
+  if (E <= 0) return hipMemsetAsync(estart_, 0, sizeof(int32_t) * (size_t)(B.ntiles + 2), s);
+  // the bucket counts (the reuse path zeroed them with its first launch); stage D's degree counts are zeroed by k_edge_count
+  if (!B.reuse) zero4(s, B.ecnt, 2 * (int64_t)V + 1);
+  hipLaunchKernelGGL(k_edge_count, grid1(std::max<int64_t>(E, (int64_t)V + 1)), dim3(256), 0, s, E, V, in.edges, A->v_o2i,
+                     tile_of_int_, B.leaf.lo, B.leaf.hi, B.ecnt, rank_, flags_, counts_);
+  HIPRET(scan_i32(s, 0, B.ecnt, B.eoff, 2 * (int64_t)V + 1, false, cub_tmp_, cub_bytes_));
+  hipLaunchKernelGGL(k_edge_fill, grid1(E), dim3(256), 0, s, E, V, in.edges, A->v_o2i, tile_of_int_, B.leaf.lo, B.leaf.hi, B.eoff,
+                     rank_, B.esorted);
+  // bucket sort + edge records + degree counts of stage D (kSegCap tiles <= 2V rows / 256 blocks * 256: the
+  // grid covers estart[0 .. ntiles] as long as 2V >= ntiles + 1, i.e. always: a tile owns a vertex)
+  hipLaunchKernelGGL(k_edge_rows_gather, grid1(std::max<int64_t>(2 * (int64_t)V, B.ntiles + 1)), dim3(256), 0, s, 2 * V, B.eoff,
+                     B.esorted, in.edges, in.alpha, in.beta, in.pos, A->v_o2i, A->e_i2o, A->e_o2i, A->eij, A->ew, V, E, B.ntiles,
+                     B.leaf.lo, estart_, edge_dsign(B.opt.d_sign), counts_, B.rank2);
+  return hipSuccess;
+}
+
+// ---- stage D: incidence CSR (degree counts and ranks: k_edge_rows_gather) ----
+hipError_t DevPlanner::incidence_csr(Build& B) {
+  DevPlanArrays* A = B.A;
+  if (B.E <= 0) return hipMemsetAsync(A->grow, 0, sizeof(int32_t) * ((size_t)B.V + 1), B.s);
+  HIPRET(scan_i32(B.s, 0, counts_, A->grow, (int64_t)B.V + 1, false, cub_tmp_, cub_bytes_));
+  hipLaunchKernelGGL(k_csr_fill, grid1(B.E), dim3(256), 0, B.s, B.E, A->eij, A->e_o2i, A->grow, B.rank2,
+                     reinterpret_cast<uint32_t*>(A->ginc));
+  hipLaunchKernelGGL(k_csr_rows<true>, grid1(B.V), dim3(256), 0, B.s, B.V, A->grow, A->e_o2i,
+                     reinterpret_cast<uint32_t*>(A->ginc), A->eij, gadj_, ipos_);
+  return hipSuccess;
+}
+
+hipError_t DevPlanner::launch_pass2(Build& B) {
+  hipLaunchKernelGGL(k_tile_pass2, dim3(B.ntiles), dim3(kP2Threads), B.lds2, B.s, B.graph(), B.leaf.lo, B.leaf.hi, estart_,
+                     tile_ext_, tile_meta_, B.tile_out());
+  B.tiles_built = true;
+  return hipGetLastError();
+}
+
+// ---- stage F: the tiles.  The tile arrays are sized from the totals pass 1 counts.  A frame stream does not wait for them: the
+// arrays are allocated for 9/8 of the PREVIOUS build's totals, pass 2 is launched right behind pass 1 and the one
+// synchronisation at the end tells whether the guess held (kPlanSpecTooSmall: the exact sizes are known by then and pass 2 is
+// simply run again).  First build on a handle: one more round trip, as before. ----
+hipError_t DevPlanner::tile_passes(Build& B) {
+  const hipStream_t s = B.s;
+  const int ntiles = B.ntiles;
+  B.spec = spec_nv_ > 0 && spec_tiles_ >= ntiles;
+  if (B.spec && B.alloc_tiles(B.alloc_ctx, (size_t)spec_tiles_, (size_t)spec_nv_, (size_t)spec_ne_, (size_t)spec_ns_) != 0)
     return hipErrorOutOfMemory;
-  const bool fused = spec && ntiles <= kScanMaxBlocks && scan_agg_[0];
-  int32_t* hflags = reinterpret_cast<int32_t*>(hpin_);
-  int32_t* huser = reinterpret_cast<int32_t*>(hpin_ + 64);
-  TileDesc* htiles = reinterpret_cast<TileDesc*>(hpin_ + 256);
-  auto tile_out = [&]() {
-    TileOut O;
-    O.ew = A->ew; O.tiles = A->tiles; O.t_vmap = A->t_vmap; O.t_emap = A->t_emap; O.t_eij = A->t_eij; O.t_ew = A->t_ew;
-    O.t_srow = A->t_srow; O.flags = flags_; O.lane_order = opt.lane_order == 2 ? 1 : 0;
-    const bool tile_prof = tlevel == 5;
-    O.prof = tile_prof ? reinterpret_cast<long long*>(wscan_) : nullptr;  // (free by now)
-    return O;
-  };
-  auto launch_pass2 = [&]() -> hipError_t {
-    hipLaunchKernelGGL(k_tile_pass2, dim3(ntiles), dim3(kP2Threads), lds2, s, G, leaf.lo, leaf.hi, estart_, tile_ext_,
-                       tile_meta_, tile_out());
-    return hipGetLastError();
-  };
-  static_assert(sizeof(TileDesc) % 4 == 0, "descriptors are published as words");
-  bool tiles_built = false;
-  auto publish = [&]() -> hipError_t {
-    const int32_t words = tiles_built ? (int32_t)(sizeof(TileDesc) / 4) * ntiles : 0;
-    hipLaunchKernelGGL(k_publish, grid1(std::max(words, 8)), dim3(256), 0, s, flags_,
-                       (user_flags_dev && user_flags_host) ? user_flags_dev : nullptr,
-                       tiles_built ? reinterpret_cast<const int32_t*>(A->tiles) : nullptr, words, hflags, huser,
-                       reinterpret_cast<int32_t*>(htiles));
-    return hipGetLastError();
-  };
-  if (fused) {
+  B.fused = B.spec && ntiles <= kScanMaxBlocks && scan_agg_[0];
+  const TileGraph G = B.graph();
+  if (B.fused) {
     // (the triangle stage on the second stream raises its flags on the same word: join first, so that
     // every tile of the launch sees the same word at its start)
-    if (tri_stage) HIPRET(hipStreamWaitEvent(s, ev_join_, 0));
+    if (B.tri_stage) HIPRET(hipStreamWaitEvent(s, ev_join_, 0));
     ScanState st;
     HIPRET(scan_state(s, scan_agg_[0], scan_flag_[0], &scan_epoch_[0], flags_, &st));
-    hipLaunchKernelGGL(k_tile_fused, dim3(ntiles), dim3(kP2Threads), lds2, s, G, leaf.lo, leaf.hi, estart_, tile_ext_,
-                       tile_meta_, tile_out(), st, spec_nv_, spec_ne_, spec_ns_);
-    tiles_built = true;
-    if (tlevel == 5) {
-      long long h[10] = {0};
-      (void)hipStreamSynchronize(s);
-      (void)hipMemcpy(h, wscan_, sizeof(h), hipMemcpyDeviceToHost);
-      std::fprintf(stderr, "[tile0] ticks: rings %lld hash %lld keys %lld lookback %lld sort %lld slot rows %lld records %lld  total %lld\n",
-                   h[2] - h[1], h[3] - h[2], h[4] - h[3], h[5] - h[4], h[6] - h[5], h[7] - h[6], h[8] - h[7], h[8] - h[1]);
-    }
-  } else {
-    hipLaunchKernelGGL(k_tile_pass1, dim3(ntiles), dim3(kP1Threads), lds1, s, G, leaf.lo, leaf.hi, tile_ext_, tile_meta_);
-    hipLaunchKernelGGL(k_tile_offsets, dim3(1), dim3(kSegCap), 0, s, ntiles, tile_meta_, flags_, spec ? spec_nv_ : 0,
-                       spec ? spec_ne_ : 0, spec ? spec_ns_ : 0);
-    if (tri_stage) HIPRET(hipStreamWaitEvent(s, ev_join_, 0));
-    if (spec) { HIPRET(launch_pass2()); tiles_built = true; }
+    hipLaunchKernelGGL(k_tile_fused, dim3(ntiles), dim3(kP2Threads), B.lds2, s, G, B.leaf.lo, B.leaf.hi, estart_, tile_ext_,
+                       tile_meta_, B.tile_out(), st, spec_nv_, spec_ne_, spec_ns_);
+    B.tiles_built = true;
+    return hipSuccess;
   }
-  lap("E tris (joined)");
-  HIPRET(publish());  // (the caller's own check word rides on the same sync)
-  if (timing_dev) (void)hipEventRecord(tev[1], s);
-  const auto t_enq = std::chrono::steady_clock::now();
+  hipLaunchKernelGGL(k_tile_pass1, dim3(ntiles), dim3(kP1Threads), B.lds1, s, G, B.leaf.lo, B.leaf.hi, tile_ext_, tile_meta_);
+  hipLaunchKernelGGL(k_tile_offsets, dim3(1), dim3(kSegCap), 0, s, ntiles, tile_meta_, flags_, B.spec ? spec_nv_ : 0,
+                     B.spec ? spec_ne_ : 0, B.spec ? spec_ns_ : 0);
+  if (B.tri_stage) HIPRET(hipStreamWaitEvent(s, ev_join_, 0));
+  return B.spec ? launch_pass2(B) : hipSuccess;
+}
+
+// What the host reads after the build, into page-locked memory (the caller's own check words ride on the same sync)
+hipError_t DevPlanner::publish(Build& B) {
+  static_assert(sizeof(TileDesc) % 4 == 0, "descriptors are published as words");
+  const int32_t words = B.tiles_built ? (int32_t)(sizeof(TileDesc) / 4) * B.ntiles : 0;
+  hipLaunchKernelGGL(k_publish, grid1(std::max(words, 8)), dim3(256), 0, B.s, flags_, B.user_dev,
+                     B.tiles_built ? reinterpret_cast<const int32_t*>(B.A->tiles) : nullptr, words, B.hflags, B.huser,
+                     reinterpret_cast<int32_t*>(B.htiles));
+  return hipGetLastError();
+}
+
+// ---- stage G (first build on a handle, or the speculative arrays were too small): pass 2 at the exact sizes ----
+hipError_t DevPlanner::rerun_pass2(Build& B, bool spec_too_small) {
+  if (B.alloc_tiles(B.alloc_ctx, (size_t)B.ntiles, (size_t)B.hflags[1], (size_t)B.hflags[2], (size_t)B.hflags[3]) != 0)
+    return hipErrorOutOfMemory;
+  if (spec_too_small) HIPRET(hipMemsetAsync(flags_, 0, sizeof(int32_t), B.s));  // (nothing else was set: plan_verdict())
+  HIPRET(launch_pass2(B));
+  HIPRET(publish(B));
+  HIPRET(hipStreamSynchronize(B.s));
+  return hipGetLastError();
+}
+
+hipError_t DevPlanner::build(hipStream_t s, const PlanOptions& opt, int32_t V, int32_t E, int32_t T, int ntiles,
+                             int depth, const DevPlanInputs& in, DevPlanArrays* A, AllocTilesFn alloc_tiles,
+                             void* alloc_ctx, std::vector<TileDesc>* tiles_host, bool* ok, bool* index_error,
+                             const int32_t* user_flags_dev, int32_t* user_flags_host,
+                             const std::function<hipError_t()>& after_partition) {
+  *ok = false;
+  *index_error = false;
+  PlanTimer tm{opt.timing, s};
+  HIPRET(reserve(V, E, T, ntiles));
+  tm.lap("reserve");
+  tm.begin();
+  if (!attr_set_) {  // per planner (= per handle = per device), not per process
+    HIPRET(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_pass1), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
+    HIPRET(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_pass2), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
+    HIPRET(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_fused), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
+    HIPRET(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mini_plan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMiniLds));
+    attr_set_ = true;
+  }
+  const bool has_user = user_flags_dev && user_flags_host;
+  const bool reuse = reuse_next_;
+  const bool mini = mini_set_ && reuse && mini_eligible(V, T, E) && ntiles <= kSegCap && expect_E_ == E;
+  mini_used_ = mini_used_ || mini;  // (sticky until the next offer: a retry after a rejected partition keeps
+  mini_set_ = false;                //  what the mini launch derived -- edges and data terms come first in it)
+  reuse_next_ = false;
+  last_reused_ = false;
+  Build B{*this, s, opt, V, E, T, ntiles, depth, in, A, alloc_tiles, alloc_ctx, has_user ? user_flags_dev : nullptr, reuse, mini,
+          weight_mode_ != 0, tm.stamps(4, wscan_), tm.stamps(5, wscan_)};
+
+  // the first launch: flags; the vertex order outputs (every entry is an index for the later stages, whatever the partition);
+  // on the reuse path its tile counters and stage C's bucket counts ride along.  Then the weights of a stream's bisection.
+  if (!mini) zero4(s, flags_, 8, A->v_o2i, V, tile_of_int_, V, reuse ? reuse_cnt_ : nullptr, (int64_t)kCntStride * ntiles,
+        (reuse && E > 0) ? B.ecnt : nullptr, 2 * (int64_t)V + 1);
+  if (weight_mode_ == 2 && !reuse)  // (mode 1: w_int_ already holds the weights, see weights_from_tiles / _scale_)
+    hipLaunchKernelGGL(k_weights_from_grid, grid1(V), dim3(256), 0, s, V, in.pos, grid_bounds_, grid_w_, w_int_);
+  if (mini) { partition_mini(B); tm.print_stamps(4, wscan_); }
+  else if (reuse) partition_reuse(B);
+  else HIPRET(partition_bisect(B));
+  B.leaf = B.tab[B.cur];
+  tm.lap("A rcb");
+  if (!mini) order_vertices(B);  // (stages B to E are part of k_mini_plan)
+  tm.lap("B morton");
+  if (after_partition) HIPRET(after_partition());  // the caller's edge / data arrays arrive now
+  B.tri_stage = T > 0 && in.tris && !mini;
+  if (B.tri_stage) HIPRET(triangle_csr(B));
+  if (!mini) HIPRET(edge_order(B));
+  tm.lap("C edges");
+  if (!mini) HIPRET(incidence_csr(B));
+  tm.lap("D csr");
+  HIPRET(tile_passes(B));
+  if (B.fused) tm.print_stamps(5, wscan_);
+  tm.lap("E tris (joined)");
+  HIPRET(publish(B));
+  tm.enqueued();
   HIPRET(hipStreamSynchronize(s));
   HIPRET(hipGetLastError());
-  if (timing_dev) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, tev[0], tev[1]);
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[plan_dev] device %.3f ms; host: enqueued after %.3f ms, synchronised after %.3f ms\n", ms,
-                 std::chrono::duration<double, std::milli>(t_enq - t_build0).count(),
-                 std::chrono::duration<double, std::milli>(now - t_build0).count());
+  tm.synchronised();
+
+  if (has_user) {
+    for (int i = 0; i < kUserWords; ++i) user_flags_host[i] = B.huser[i];
+    // the flags of the edge derivation in front of this build (edges_from_tris without a round trip)
+    const PlanVerdict chain = plan_verdict(user_flags_host[kUserChainFlags]);
+    if (chain == PlanVerdict::kIndexError) *index_error = true;  // triangle index out of range
+    if (chain != PlanVerdict::kOk) return hipSuccess;            // (or a look-back timeout: not ok)
   }
-  if (user_flags_dev && user_flags_host) {
-    for (int i = 0; i < 4; ++i) user_flags_host[i] = huser[i];
-    // word 2: the flags of the edge derivation in front of this build (edges_from_tris without a round trip)
-    if (user_flags_host[2] & 32) return hipSuccess;                          // look-back timeout: not ok
-    if (user_flags_host[2] & 2) { *index_error = true; return hipSuccess; }  // triangle index out of range
-  }
-  lap(spec ? "F+G pass1+2+sync" : "F pass1+sync");
-  // word 0: the caller's failure flag; word 1: the number of edges the graph sync derived -- a build
-  // that was launched on a PREDICTED edge count and got it wrong is worthless whatever else it says
-  if (user_flags_dev && user_flags_host && (user_flags_host[0] || (expect_E_ >= 0 && user_flags_host[1] != expect_E_)))
+  tm.lap(B.spec ? "F+G pass1+2+sync" : "F pass1+sync");
+  // the caller's failure word; the number of edges the graph sync derived -- a build that was launched on a PREDICTED edge
+  // count and got it wrong is worthless whatever else it says
+  if (has_user && (user_flags_host[kUserNonFinite] || (expect_E_ >= 0 && user_flags_host[kUserEdgeCount] != expect_E_)))
     return hipSuccess;
-  if (hflags[0] & 32) return hipSuccess;  // a scan's look-back timed out (never seen): not ok -> host builder
-  if (hflags[0] & 64) { map_tiles_ = 0; return hipSuccess; }  // the reused partition does not suit this frame: not ok
-  if (hflags[0] & 2) { *index_error = true; return hipSuccess; }
-  if (hflags[0] & 16) {  // a subtree outgrew its workgroup (uneven weighted splits): hand over one
-    // level later from now on; after three such steps every level goes through the global kernels
-    if (++sub_extra_levels_ > 3) use_subtree_ = false;
-    return build(s, opt, V, E, T, ntiles, depth, in, A, alloc_tiles, alloc_ctx, tiles_host, ok, index_error,
-                 user_flags_dev, user_flags_host, nullptr);  // (the caller's arrays are staged by now)
+  const int32_t* hflags = B.hflags;
+  const PlanVerdict v = plan_verdict(hflags[0]);
+  switch (v) {
+    case PlanVerdict::kRejectedReuse: map_tiles_ = 0; return hipSuccess;
+    case PlanVerdict::kRejected: return hipSuccess;
+    case PlanVerdict::kIndexError: *index_error = true; return hipSuccess;
+    case PlanVerdict::kRetrySubtree:  // (uneven weighted splits) after three such steps every level goes through the global kernels
+      if (++sub_extra_levels_ > 3) use_subtree_ = false;
+      return build(s, opt, V, E, T, ntiles, depth, in, A, alloc_tiles, alloc_ctx, tiles_host, ok, index_error,
+                   user_flags_dev, user_flags_host, nullptr);  // (the caller's arrays are staged by now)
+    default: break;  // (the totals are valid)
   }
-  if (hflags[0] & 5) return hipSuccess;  // a tile does not fit (or the partition is inconsistent): not ok
   // the next build on this handle speculates on these totals
   spec_tiles_ = std::max(ntiles, spec_tiles_);
   spec_nv_ = hflags[1] + hflags[1] / 8 + 1024; spec_ne_ = hflags[2] + hflags[2] / 8 + 1024; spec_ns_ = hflags[3] + hflags[3] / 8 + 1024;
-  if (!spec || (hflags[0] & 128)) {
-    if (alloc_tiles(alloc_ctx, (size_t)ntiles, (size_t)hflags[1], (size_t)hflags[2], (size_t)hflags[3]) != 0)
-      return hipErrorOutOfMemory;
-    // ---- stage G (first build on a handle, or the speculative arrays were too small) ----
-    if (hflags[0] & 128) HIPRET(hipMemsetAsync(flags_, 0, sizeof(int32_t), s));  // (nothing else was set: checked above)
-    HIPRET(launch_pass2());
-    tiles_built = true;
-    HIPRET(publish());
-    HIPRET(hipStreamSynchronize(s));
-    HIPRET(hipGetLastError());
-    lap("G pass2+sync");
+  if (!B.spec || v == PlanVerdict::kSpecTooSmall) {
+    HIPRET(rerun_pass2(B, v == PlanVerdict::kSpecTooSmall));
+    tm.lap("G pass2+sync");
   }
-  tiles_host->assign(htiles, htiles + ntiles);
-  if (hflags[0] & (8 | 32)) return hipSuccess;
+  tiles_host->assign(B.htiles, B.htiles + ntiles);
+  if (plan_verdict(hflags[0]) != PlanVerdict::kOk) return hipSuccess;  // (a tile pass failed)
   *ok = true;
   return hipGetLastError();
 }
@@ -2995,7 +3047,7 @@ hipError_t DevPlanner::edges_from_tris(hipStream_t s, int32_t V, int32_t T, cons
   // nan_flag[2] -- the build() that follows zeroes flags_ with its first launch and reads the caller's
   // words at its first synchronisation
   const bool own_flags = expected_E >= 0 && nan_flag;
-  int32_t* he_flags = own_flags ? nan_flag + 2 : flags_;
+  int32_t* he_flags = own_flags ? nan_flag + kUserChainFlags : flags_;
   int32_t* f = reinterpret_cast<int32_t*>(vals_a_);
   int32_t* idx = reinterpret_cast<int32_t*>(vals_b_);
   int32_t* cnt = tcnt_;                                     // V + 1 counts
@@ -3009,7 +3061,7 @@ hipError_t DevPlanner::edges_from_tris(hipStream_t s, int32_t V, int32_t T, cons
   // (the half-edge kernels above read the triangles only: the caller stages the positions now, its
   // host-synchronous copy runs beside them)
   if (before_positions) HIPRET(before_positions());
-  int32_t* total = (expected_E >= 0 && nan_flag) ? nan_flag + 1 : flags_ + 4;
+  int32_t* total = own_flags ? nan_flag + kUserEdgeCount : flags_ + 4;
   if (fused) {
     ScanState st;
     HIPRET(scan_state(s, scan_agg_[0], scan_flag_[0], &scan_epoch_[0], he_flags, &st));
@@ -3033,8 +3085,9 @@ hipError_t DevPlanner::edges_from_tris(hipStream_t s, int32_t V, int32_t T, cons
   if (while_running) while_running();  // host work of the caller overlaps the kernels above
   HIPRET(hipStreamSynchronize(s));
   HIPRET(hipGetLastError());
-  if (h[0] & 32) return hipErrorUnknown;  // a scan's look-back timed out (never seen)
-  if (h[0] & 2) { *index_error = true; return hipSuccess; }
+  const PlanVerdict v = plan_verdict(h[0]);  // (the chain raises kPlanLookbackTimeout -- never seen -- and kPlanBadIndex)
+  if (v == PlanVerdict::kRejected) return hipErrorUnknown;
+  if (v == PlanVerdict::kIndexError) { *index_error = true; return hipSuccess; }
   *E_out = h[4];
   return hipSuccess;
 }
@@ -3047,7 +3100,7 @@ __global__ __launch_bounds__(256) void k_check_finite5(FiniteJob j, int32_t* fla
   bool bad = false;
   for (int a = 0; a < 5; ++a)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < j.n[a]; i += stride) bad |= !isfinite(j.p[a][i]);
-  if (bad) atomicOr(flags, 1);
+  if (bad) atomicOr(&flags[kUserNonFinite], kUserNonFiniteBit);
 }
 
 hipError_t DevPlanner::check_finite(hipStream_t s, int32_t* flags, const float* a, int64_t na, const float* b, int64_t nb,

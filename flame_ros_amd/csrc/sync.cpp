@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "../../include/flame_hip.h"
+#include "common.h"
 
 namespace flamehip {
 
@@ -16,12 +17,12 @@ int graph_sync_host(const flame_hip_sync_params& sp, int32_t V, int32_t T, const
   std::vector<int32_t>& cnt = out->scratch_cnt;
   std::vector<int32_t>& hi = out->scratch_hi;
   cnt.assign((size_t)V + 1, 0);
-  for (int32_t t = 0; t < T; ++t) {
-    const int32_t a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];
-    if (a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V || a == b || b == c || a == c)
-      return FLAME_HIP_ERR_ARG;
-    cnt[std::min(a, b) + 1]++; cnt[std::min(b, c) + 1]++; cnt[std::min(c, a) + 1]++;
-  }
+  for (int32_t t = 0; t < T; ++t)
+    for (int k = 0; k < 3; ++k) {
+      int32_t lo, hi_end;
+      if (!tri_side(tris[3 * t + k], tris[3 * t + (k + 1) % 3], V, &lo, &hi_end)) return FLAME_HIP_ERR_ARG;
+      cnt[lo + 1]++;
+    }
   for (int32_t v = 0; v < V; ++v) cnt[v + 1] += cnt[v];
   hi.resize(3 * (size_t)T);
   {
@@ -29,8 +30,9 @@ int graph_sync_host(const flame_hip_sync_params& sp, int32_t V, int32_t T, const
     fill.assign(cnt.begin(), cnt.end() - 1);
     for (int32_t t = 0; t < T; ++t)
       for (int k = 0; k < 3; ++k) {
-        const int32_t a = tris[3 * t + k], b = tris[3 * t + (k + 1) % 3];
-        hi[fill[std::min(a, b)]++] = std::max(a, b);
+        int32_t lo, hi_end;
+        (void)tri_side(tris[3 * t + k], tris[3 * t + (k + 1) % 3], V, &lo, &hi_end);
+        hi[fill[lo]++] = hi_end;
       }
   }
   out->edges.clear();
@@ -51,9 +53,7 @@ int graph_sync_host(const flame_hip_sync_params& sp, int32_t V, int32_t T, const
   for (int32_t e = 0; e < E; ++e) {
     const int32_t i = out->edges[2 * e], j = out->edges[2 * e + 1];
     const float dx = pos[2 * i] - pos[2 * j], dy = pos[2 * i + 1] - pos[2 * j + 1];
-    // this file is compiled with -ffp-contract=off: dx*dx + dy*dy is two roundings, as the
-    // oracle states it
-    const float inv = 1.0f / std::sqrt(dx * dx + dy * dy);
+    const float inv = edge_alpha(dx, dy);  // (this file too is compiled with -ffp-contract=off)
     if (!custom) { out->alpha[e] = inv; continue; }
     float a = (rule == 1 || rule == 3) ? 1.0f : inv;
     float b = (rule == 1 || rule == 2) ? 1.0f : inv;
@@ -71,10 +71,9 @@ int graph_sync_host(const flame_hip_sync_params& sp, int32_t V, int32_t T, const
   }
   out->z.resize(V); out->wgt.resize(V); out->x0.resize(V);
   for (int32_t v = 0; v < V; ++v) {
-    out->z[v] = mu[v] / scale;
-    out->wgt[v] = sp.adaptive_data_weights ? 1.0f / var[v] : 1.0f;
-    out->x0[v] = (sp.init_with_prediction && prediction && std::isfinite(prediction[v]))
-                     ? prediction[v] / scale : out->z[v];
+    const DataTerm d = data_term(mu[v], sp.adaptive_data_weights ? var[v] : 1.0f,
+                                 (sp.init_with_prediction && prediction) ? prediction[v] : NAN, scale, sp.adaptive_data_weights != 0);
+    out->z[v] = d.z; out->wgt[v] = d.wgt; out->x0[v] = d.x0;
   }
   out->scale = scale;
   return 0;
