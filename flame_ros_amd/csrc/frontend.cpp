@@ -9,7 +9,9 @@
 // from them and the frame's pose.  flame_hip_frontend_set_cost records the matching cost (SSD / ZSSD); every frame forms the BAD_MATCH
 // threshold of that cost and picks the tracker's instantiation; flame_hip_frontend_set_gain_invariant puts the gain-invariant cost in
 // their place while it is on.  flame_hip_frontend_set_ref_grad records the reference-patch gradient
-// gate; while it is on every frame forms the epipole table behind the pose table and runs the tracker's gated instantiation.  Reads
+// gate; while it is on every frame forms the epipole table behind the pose table and runs the tracker's gated instantiation.
+// flame_hip_frontend_set_warp records the warped-window switch; while it is on every frame runs the tracker's warped instantiation
+// (it reads the pose table and the intrinsics the frame holds anyway).  Reads
 // no environment variable.
 #include <hip/hip_runtime.h>
 
@@ -77,6 +79,8 @@ struct flame_hip_frontend {
   int32_t cost_mode = FLAME_HIP_FE_COST_SSD;
   // the gain-invariant cost (set_gain_invariant): while on it overrides cost_mode, which stays what set_cost set; no state either
   int32_t gain_invariant = 0;
+  // the warped window (set_warp): no state depends on it either
+  int32_t warp = 0;
   // reference-patch gradient gate (set_ref_grad): 0 = off; no state depends on it either
   float min_epi_grad = 0.f;
 };
@@ -375,7 +379,7 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
   FE_HIP(hipMemsetAsync(fe->d_cell_key, 0xFF, (sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)ncells, s));
   FE_HIP(hipMemsetAsync(fe->d_counts, 0, sizeof(int32_t) * kFeCounts, s));
   if (overwrote) fe_launch_kill(s, f, valid_mask(fe));
-  fe_launch_track(s, f, cost, ref_grad);
+  fe_launch_track(s, f, cost, ref_grad, fe->warp != 0);
   if (is_poseframe) fe_launch_detect(s, f);
   fe_launch_compact(s, f);
   FE_HIP(hipGetLastError());
@@ -484,6 +488,12 @@ int flame_hip_frontend_set_cost(flame_hip_frontend* fe, int32_t mode) {
 int flame_hip_frontend_set_gain_invariant(flame_hip_frontend* fe, int32_t on) {
   if (!fe || (on != 0 && on != 1)) return FLAME_HIP_ERR_ARG;
   fe->gain_invariant = on;  // takes effect with the next frame; cost_mode stays what set_cost set
+  return 0;
+}
+
+int flame_hip_frontend_set_warp(flame_hip_frontend* fe, int32_t on) {
+  if (!fe || (on != 0 && on != 1)) return FLAME_HIP_ERR_ARG;
+  fe->warp = on;  // takes effect with the next frame
   return 0;
 }
 
@@ -651,6 +661,8 @@ int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* va
   if (!std::strcmp(key, "gates")) { *value = (fe->gates.letterbox ? 1 : 0) | (fe->gates.height_gate ? 2 : 0); return 0; }
   if (!std::strcmp(key, "cost_mode")) { *value = fe->cost_mode; return 0; }
   if (!std::strcmp(key, "gain_invariant")) { *value = fe->gain_invariant; return 0; }
+  if (!std::strcmp(key, "warp")) { *value = fe->warp; return 0; }
+  if (!std::strcmp(key, "warp_refused")) { *value = fe->counts[13]; return 0; }
   if (!std::strcmp(key, "ref_grad")) { *value = fe->min_epi_grad > 0.f ? 1 : 0; return 0; }
   if (!std::strcmp(key, "fail_ref_grad")) { *value = fe->counts[12]; return 0; }
   if (!std::strcmp(key, "held_height")) { *value = fe->counts[10]; return 0; }

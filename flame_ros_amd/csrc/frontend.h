@@ -16,7 +16,8 @@ constexpr int kFeMaxWin = 9;
 enum { kFeOk = 0, kFeNoParallax = 1, kFeOutside = 2, kFeBadMatch = 3, kFeAmbiguous = 4, kFeNew = 5, kFeDied = 6, kFeRefGrad = 7, kFeFree = -1 };
 constexpr int kFeCounts = 16;  // counts[]: 0 = emitted, 1 = live, 2 + status = features of that status (0..6), 9 = detections dropped (no free slot),
                                // 10 = features held by the height gate, 11 = projections refused by the letterbox,
-                               // 12 = features of status kFeRefGrad (2 + 7 is taken)
+                               // 12 = features of status kFeRefGrad (2 + 7 is taken),
+                               // 13 = features the warped window refused (they are among the kFeOutside ones as well)
 
 // A = K R and c = K t of T_cur_ref, rounded once to float32 on the host (one record per pose-frame ring slot)
 struct FePose {
@@ -118,8 +119,9 @@ struct FeFrame {
 
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask);
 // cost: the matching cost of the frame (f.bad_match_cost is that cost's threshold); ref_grad: the reference-patch gradient gate (f.min_epi_grad, f.epi)
+// warp: the warped window (reads nothing beyond poses, fx, fy; counts[13])
 enum { kFeCostSsd = 0, kFeCostZssd = 1, kFeCostGi = 2 };
-void fe_launch_track(hipStream_t s, const FeFrame& f, int cost, bool ref_grad);
+void fe_launch_track(hipStream_t s, const FeFrame& f, int cost, bool ref_grad, bool warp);
 void fe_launch_detect(hipStream_t s, const FeFrame& f);
 void fe_launch_compact(hipStream_t s, const FeFrame& f);
 

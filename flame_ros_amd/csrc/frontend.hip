@@ -147,6 +147,96 @@ __device__ __forceinline__ unsigned long long fe_cost_gi(const FeFrame& f, const
   return Cd > 0.0 ? (unsigned long long)floor(Cd) : 0ull;
 }
 
+// The warped window (DESIGN.md 5.3 "Warped window", flame_hip_frontend_set_warp): the current image is sampled where the reference
+// window's pixels land under the pose change, an affine map J taken once per feature at the prior clamped into the searched
+// interval.  fe_warp_jq forms J = d(projection)/d(reference pixel) in float32 (no fmaf; gx_r = A[r][0] / fx, gy_r = A[r][1] / fy
+// are the derivatives of a = A b), quantises each entry to 1/256 (Jq = floorf(256 J + 0.5f), refused unless that float is finite
+// and at most 1024 in magnitude: a stretch of 4) and tests det Jq >= 4096 (an area scale of 1/16; no mirrored or collapsed map).
+// Everything here is wave-uniform: the caller keeps the four integers and the verdict in scalar registers.
+struct FeJq {
+  int j00, j01, j10, j11;
+};
+__device__ __forceinline__ bool fe_warp_q(float J, int* q) {
+  const float fq = floorf(J * 256.0f + 0.5f);
+  const bool ok = __builtin_fabsf(fq) <= 1024.0f;  // (a NaN fails, an infinity fails)
+  *q = __builtin_amdgcn_readfirstlane(ok ? (int)fq : 0);
+  return ok;
+}
+__device__ __forceinline__ bool fe_warp_jq(const FeFrame& f, const FePose& P, float a0, float a1, float a2, float mu, float xi0,
+                                           float xi1, FeJq* Jq) {
+  const float t = mu > xi0 ? mu : xi0;
+  const float xj = t < xi1 ? t : xi1;
+  const float w0 = a0 + xj * P.c[0], w1 = a1 + xj * P.c[1], w2 = a2 + xj * P.c[2];
+  const float px = w0 / w2, py = w1 / w2;
+  const float gx0 = P.A[0] / f.fx, gx1 = P.A[3] / f.fx, gx2 = P.A[6] / f.fx;
+  const float gy0 = P.A[1] / f.fy, gy1 = P.A[4] / f.fy, gy2 = P.A[7] / f.fy;
+  bool ok = fe_warp_q((gx0 - px * gx2) / w2, &Jq->j00);
+  ok = fe_warp_q((gy0 - px * gy2) / w2, &Jq->j01) && ok;
+  ok = fe_warp_q((gx1 - py * gx2) / w2, &Jq->j10) && ok;
+  ok = fe_warp_q((gy1 - py * gy2) / w2, &Jq->j11) && ok;
+  const int det = Jq->j00 * Jq->j11 - Jq->j01 * Jq->j10;  // (|.| <= 2^21)
+  return __builtin_amdgcn_readfirstlane((int)(ok && det >= 4096)) != 0;
+}
+
+// Cost of one sample under the warp, the one sampler of the three costs: window offset (i, j) of the reference window is compared
+// with the current image at (qx, qy) + ((Jq (i, j) + 8) >> 4) sixteenths of a pixel (an arithmetic shift: it floors), bilinear
+// with that position's own sixteenths -- four byte loads per window pixel.  The offsets are floors of a map linear in i and in j,
+// so their extremes over the window sit at its four corners: testing the corners (and their +1 neighbours) tests every pixel.
+// Jq = (256, 0, 0, 256) gives ox = qx + 16 i: the unwarped integers.  I feeds the sums of the cost COST exactly as in fe_cost /
+// fe_cost_gi, whose bounds hold unchanged (I <= 65 280).
+template <int COST>
+__device__ __forceinline__ unsigned long long fe_cost_warp(const FeFrame& f, const uint8_t* __restrict__ ref, int u, int v, float px,
+                                                           float py, const FeJq& Jq, unsigned int SR, unsigned long long ZR) {
+  const float fqx = floorf(px * 16.0f + 0.5f), fqy = floorf(py * 16.0f + 0.5f);
+  if (!(fqx >= 0.0f && fqx <= (float)(16 * f.W) && fqy >= 0.0f && fqy <= (float)(16 * f.H))) return kNone;
+  const int qx = (int)fqx, qy = (int)fqy;
+  const int r = f.win >> 1;
+#pragma unroll
+  for (int corner = 0; corner < 4; ++corner) {
+    const int i = corner & 1 ? r : -r, j = corner & 2 ? r : -r;
+    const int x = (qx + ((Jq.j00 * i + Jq.j01 * j + 8) >> 4)) >> 4, y = (qy + ((Jq.j10 * i + Jq.j11 * j + 8) >> 4)) >> 4;
+    if (x < 0 || y < 0 || x + 1 > f.W - 1 || y + 1 > f.H - 1) return kNone;
+  }
+  unsigned long long S2 = 0, SIR = 0;  // sum D^2 (SSD, ZSSD) or sum I^2 (GI); sum I R (GI)
+  int S1 = 0;                          // sum D (ZSSD) or sum I (GI)
+  for (int j = -r; j <= r; ++j) {
+    const uint8_t* __restrict__ rr = ref + (size_t)(v + j) * f.W + u;
+    for (int i = -r; i <= r; ++i) {
+      const int ox = qx + ((Jq.j00 * i + Jq.j01 * j + 8) >> 4), oy = qy + ((Jq.j10 * i + Jq.j11 * j + 8) >> 4);
+      const uint8_t* __restrict__ q = f.cur + (size_t)(oy >> 4) * f.W + (ox >> 4);
+      const int wx1 = ox & 15, wx0 = 16 - wx1, wy1 = oy & 15, wy0 = 16 - wy1;
+      const int I = wy0 * (wx0 * (int)q[0] + wx1 * (int)q[1]) + wy1 * (wx0 * (int)q[f.W] + wx1 * (int)q[f.W + 1]);  // <= 65 280
+      const int R = 256 * (int)rr[i];
+      if constexpr (COST == kFeCostGi) {
+        S1 += I;
+        S2 += (unsigned long long)((unsigned int)I * (unsigned int)I);  // (both products fit 32 bits)
+        SIR += (unsigned long long)((unsigned int)I * (unsigned int)R);
+      } else {
+        const int D = I - R;
+        const unsigned int aD = (unsigned int)(D < 0 ? -D : D);
+        S2 += (unsigned long long)(aD * aD);
+        if (COST == kFeCostZssd) S1 += D;
+      }
+    }
+  }
+  const unsigned long long n = (unsigned long long)(unsigned int)(f.win * f.win);
+  if constexpr (COST == kFeCostGi) {
+    const unsigned long long SI = (unsigned long long)(unsigned int)S1;
+    const unsigned long long ZI = n * S2 - SI * SI;
+    const long long ZIR = (long long)(n * SIR) - (long long)(SI * (unsigned long long)SR);
+    if (ZI == 0ull || ZIR <= 0ll) return ZR;
+    const double z = (double)ZIR;
+    const double q = (z * z) / (double)ZI;
+    const double Cd = (double)ZR - q;
+    return Cd > 0.0 ? (unsigned long long)floor(Cd) : 0ull;
+  } else if constexpr (COST == kFeCostZssd) {
+    const unsigned int a1 = (unsigned int)(S1 < 0 ? -S1 : S1);
+    return n * S2 - (unsigned long long)a1 * (unsigned long long)a1;
+  } else {
+    return S2;
+  }
+}
+
 // The reference-patch gradient gate (DESIGN.md 5.3 "Reference-patch gradient"): does the win x win reference window have structure
 // ALONG the epipolar line?  The 64 lanes cover the n <= 81 window pixels in two passes; the three sums of the structure tensor are
 // integers (each <= 81 * 255^2 < 2^24: exact as float32) and an xor butterfly leaves them in every lane, so the result is
@@ -192,7 +282,10 @@ __global__ __launch_bounds__(256) void k_fe_kill(FeFrame f, unsigned long long v
 // threshold for that cost.  Everything behind the cost -- argmin, BAD_MATCH, AMBIGUOUS, the parabola -- takes it as it comes; the
 // gain-invariant cost adds one decision, BAD_MATCH for a flat reference window (ZR == 0: nothing to correlate).  RG puts the
 // reference-patch gradient gate between the NO_PARALLAX test and the search; the instantiations without it hold none of its code.
-template <int COST, bool RG>
+// WARP samples the current image through the feature's quantised affine map (fe_warp_jq, fe_cost_warp) and refuses, behind the
+// gradient gate and before the search, a feature whose map is out of range: OUTSIDE, counted in counts[13] as well, no search
+// record.  The instantiations without it hold none of its code either.
+template <int COST, bool RG, bool WARP>
 __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
   const int lane = threadIdx.x & 63;
   const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -230,6 +323,7 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
   float mu_new = mu, var_new = var;
   float4 seg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the search record: stays zero when no search runs
   int steps = 0;
+  bool warp_refused = false;
   if (!(d0 > 0.0f && d1 > 0.0f) || !ref_in) {
     status = kFeOutside;  // an end of the search lies behind the camera / the reference patch leaves its image
   } else {
@@ -238,10 +332,14 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
     const float dx = x1 - x0, dy = y1 - y0;
     const float L = sqrtf(dx * dx + dy * dy);
     int rg = kFeOk;
+    FeJq Jq = {256, 0, 0, 256};
     if (!(L >= 2.0f)) {
       status = kFeNoParallax;
     } else if (RG && (rg = fe_ref_grad(f, ref, p, u, v, lane)) != kFeOk) {
       status = rg;  // no structure along the epipolar line (or the window's ring leaves the image): no search, a failure
+    } else if (WARP && !fe_warp_jq(f, P, a0, a1, a2, mu, xi0, xi1, &Jq)) {
+      status = kFeOutside;  // the window's map is out of range (stretch > 4, area < 1/16, mirrored): no search, a failure
+      warp_refused = true;
     } else {
       const int S = L >= (float)kFeMaxSamples ? kFeMaxSamples : (int)ceilf(L);
       const float ex = dx / (float)S, ey = dy / (float)S;
@@ -257,7 +355,8 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
         const int k = lane + 64 * pass;
         unsigned long long c = kNone;
         if (64 * pass <= S && k <= S) {
-          if constexpr (COST == kFeCostGi) c = fe_cost_gi(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey, SR, ZR);
+          if constexpr (WARP) c = fe_cost_warp<COST>(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey, Jq, SR, ZR);
+          else if constexpr (COST == kFeCostGi) c = fe_cost_gi(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey, SR, ZR);
           else c = fe_cost<COST == kFeCostZssd>(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey);
         }
         C[pass] = c;
@@ -372,6 +471,7 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
     f.steps[slot] = steps;
     atomicAdd(&f.counts[RG && status == kFeRefGrad ? 12 : 2 + status], 1);
     if (refused) atomicAdd(&f.counts[11], 1);
+    if (WARP && warp_refused) atomicAdd(&f.counts[13], 1);
     if (dies) {
       f.alive[slot] = 0;
       f.status[slot] = kFeDied;
@@ -532,16 +632,20 @@ __global__ __launch_bounds__(1024) void k_fe_compact(FeFrame f) {
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask) {
   hipLaunchKernelGGL(k_fe_kill, dim3((f.max_features + 255) / 256), dim3(256), 0, s, f, valid_mask);
 }
-void fe_launch_track(hipStream_t s, const FeFrame& f, int cost, bool ref_grad) {
+template <bool RG, bool WARP>
+static void fe_launch_track_cost(hipStream_t s, const FeFrame& f, int cost) {
   const dim3 grid((f.max_features + 3) / 4), block(256);
-  if (ref_grad) {
-    if (cost == kFeCostGi) hipLaunchKernelGGL((k_fe_track<kFeCostGi, true>), grid, block, 0, s, f);
-    else if (cost == kFeCostZssd) hipLaunchKernelGGL((k_fe_track<kFeCostZssd, true>), grid, block, 0, s, f);
-    else hipLaunchKernelGGL((k_fe_track<kFeCostSsd, true>), grid, block, 0, s, f);
+  if (cost == kFeCostGi) hipLaunchKernelGGL((k_fe_track<kFeCostGi, RG, WARP>), grid, block, 0, s, f);
+  else if (cost == kFeCostZssd) hipLaunchKernelGGL((k_fe_track<kFeCostZssd, RG, WARP>), grid, block, 0, s, f);
+  else hipLaunchKernelGGL((k_fe_track<kFeCostSsd, RG, WARP>), grid, block, 0, s, f);
+}
+void fe_launch_track(hipStream_t s, const FeFrame& f, int cost, bool ref_grad, bool warp) {
+  if (warp) {
+    if (ref_grad) fe_launch_track_cost<true, true>(s, f, cost);
+    else fe_launch_track_cost<false, true>(s, f, cost);
   } else {
-    if (cost == kFeCostGi) hipLaunchKernelGGL((k_fe_track<kFeCostGi, false>), grid, block, 0, s, f);
-    else if (cost == kFeCostZssd) hipLaunchKernelGGL((k_fe_track<kFeCostZssd, false>), grid, block, 0, s, f);
-    else hipLaunchKernelGGL((k_fe_track<kFeCostSsd, false>), grid, block, 0, s, f);
+    if (ref_grad) fe_launch_track_cost<true, false>(s, f, cost);
+    else fe_launch_track_cost<false, false>(s, f, cost);
   }
 }
 void fe_launch_detect(hipStream_t s, const FeFrame& f) {

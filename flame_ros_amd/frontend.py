@@ -139,6 +139,14 @@ class GpuFrontEnd:
         choice.  May change between any two frames."""
         _l.check(self._lib.flame_hip_frontend_set_gain_invariant(self._h, 1 if on else 0), "flame_hip_frontend_set_gain_invariant")
 
+    def set_warp(self, on=True):
+        """The warped matching window for the frames to come: the current image is sampled where the reference window's pixels land
+        under the pose change (an affine map per feature and frame, taken at the prior) -- for cameras that roll or change their
+        distance against the pose frame.  A feature whose map is out of range (a stretch above 4, an area scale below 1/16,
+        mirrored) is refused: OUTSIDE, counted in info key "warp_refused".  Under a pure sideways translation it changes no bit.
+        May change between any two frames."""
+        _l.check(self._lib.flame_hip_frontend_set_warp(self._h, 1 if on else 0), "flame_hip_frontend_set_warp")
+
     def set_ref_grad(self, min_grad):
         """The reference-patch gradient gate of the frames to come: a feature whose reference window has a root-mean-square grey
         gradient below `min_grad` ALONG its epipolar line (an edge parallel to the line: the aperture problem) is not searched and

@@ -40,6 +40,11 @@
 // line is not searched); setRefGrad() changes it later, between any two frames.  With the switch at 0 no call is made at all and
 // `num_fail_ref_patch_grad` stays unset.  A refusal (a negative or non-finite value) lands in lastError() and fails every track()
 // until a call succeeds.
+//
+// WARPED WINDOW (flame_hip.h, flame_hip_frontend_set_warp; DESIGN.md 5.3 "Warped window"): the constructor honours
+// Params::warp_matching_window (this build's own switch: the matching window follows the camera's roll and change of distance
+// against the pose frame); setWarp() changes it later, between any two frames.  With the switch off no call is made at all and
+// `num_fail_warp` stays unset.  A refusal lands in lastError() and fails every track() until a call succeeds.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -86,6 +91,11 @@ class GpuFrontEnd {
     if (handle_ && params.min_epipolar_grad != 0.f) {  // (off: no call at all)
       const int before = last_error_;
       setRefGrad(params.min_epipolar_grad);
+      if (before) last_error_ = before;  // (an earlier refusal stays what lastError() shows)
+    }
+    if (handle_ && params.warp_matching_window) {  // (off: no call at all)
+      const int before = last_error_;
+      setWarp(true);
       if (before) last_error_ = before;  // (an earlier refusal stays what lastError() shows)
     }
   }
@@ -176,6 +186,18 @@ class GpuFrontEnd {
   }
   float refGrad() const { return min_epipolar_grad_; }
 
+  // The warped matching window of the frames to come (true): the current image is sampled where the reference window's pixels land
+  // under the pose change; false (the default): the axis-aligned window.  May change between any two frames.  false (lastError())
+  // when the library refuses; track() then fails until a call succeeds.
+  bool setWarp(bool on) {
+    if (!handle_) return false;
+    warp_error_ = flame_hip_frontend_set_warp(handle_, on ? 1 : 0);
+    last_error_ = warp_error_;
+    if (!warp_error_) warp_ = on;
+    return warp_error_ == 0;
+  }
+  bool warp() const { return warp_; }
+
   // The ingest stage alone (flame_hip_frontend_rectify): `out` becomes the width x height rectified image of `raw`; the
   // feature state is untouched.
   bool rectify(const Image1b& raw, Image1b* out) {
@@ -221,6 +243,7 @@ class GpuFrontEnd {
     if (cost_error_) return fail(cost_error_);    // (nor a refused matching cost)
     if (gain_invariant_error_) return fail(gain_invariant_error_);
     if (ref_grad_error_) return fail(ref_grad_error_);  // (nor a refused gradient gate)
+    if (warp_error_) return fail(warp_error_);          // (nor a refused warp switch)
     rectified_valid_ = false;
     const int rows = have_camera_ ? raw_height_ : height_, cols = have_camera_ ? raw_width_ : width_;
     if (!in.img || !out || in.img->rows != rows || in.img->cols != cols) return fail(FLAME_HIP_ERR_ARG);
@@ -258,7 +281,8 @@ class GpuFrontEnd {
   // The tracking stats FlameStats carries (reference src/utils.cc:124-129), from the counts of the frame just tracked
   // (flame_hip_frontend_info): features whose idepth was updated, features that died of too many dropouts, ambiguous matches,
   // matches above the cost threshold.  `num_fail_max_var` is Flame's own (its variance gate); `num_fail_ref_patch_grad` is
-  // the features the reference-patch gradient gate refused and is set only while that gate is on (it is off by default: unset).
+  // the features the reference-patch gradient gate refused and is set only while that gate is on (it is off by default: unset);
+  // `num_fail_warp` is the features the warped window refused and is set only while that switch is on.
   void reportStats(utils::StatsTracker* stats) const {
     if (!handle_ || !stats) return;
     static const char* const kKeys[4][2] = {{"num_idepth_updates", "ok"}, {"num_fail_max_dropouts", "died"},
@@ -275,6 +299,9 @@ class GpuFrontEnd {
     }
     if (flame_hip_frontend_info(handle_, "ref_grad", &g) == 0 && g != 0) {
       if (flame_hip_frontend_info(handle_, "fail_ref_grad", &v) == 0) stats->set("num_fail_ref_patch_grad", static_cast<double>(v));
+    }
+    if (flame_hip_frontend_info(handle_, "warp", &g) == 0 && g != 0) {
+      if (flame_hip_frontend_info(handle_, "warp_refused", &v) == 0) stats->set("num_fail_warp", static_cast<double>(v));
     }
   }
 
@@ -309,6 +336,8 @@ class GpuFrontEnd {
   int gain_invariant_error_ = 0;  // ... and to the last gain-invariant switch
   float min_epipolar_grad_ = 0.f;
   int ref_grad_error_ = 0;  // ... and to the last gradient gate
+  bool warp_ = false;
+  int warp_error_ = 0;      // ... and to the last warp switch
   flame_hip_frontend* handle_ = nullptr;
   int last_error_ = 0;
 };

@@ -90,6 +90,13 @@ struct Params {
   // choice).  0 = off, the default: with it off the front end makes exactly the calls it made before and the key stays unset.
   // Any other registered FrontEnd gets the field carried and has to honour it itself.
   float min_epipolar_grad = 0.f;
+  // (this build's own) true = the warped matching window of flame::GpuFrontEnd's tracker (gpu_frontend.h; DESIGN.md 5.3 "Warped
+  // window"; flame_hip_frontend_set_warp): the current image is sampled where the reference window's pixels land under the pose
+  // change -- an affine map per feature and frame, taken at the prior -- so that a camera that rolls or changes its distance
+  // against the pose frame keeps its features.  A feature whose map is out of range (a stretch above 4, an area scale below 1/16)
+  // fails like one outside the image; `num_fail_warp` counts them.  Off by default: with it off the front end makes exactly the
+  // calls it made before and the key stays unset.  Any other registered FrontEnd gets the field carried and has to honour it itself.
+  bool warp_matching_window = false;
   // features (:209-231)
   // do_letterbox ("Process only middle third of image"): honoured by flame::GpuFrontEnd (gpu_frontend.h; DESIGN.md 5.3 "Gates")
   bool do_letterbox = false;

@@ -558,7 +558,7 @@ int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* 
  * call uploaded); "gates" (bit 0 = letterbox, bit 1 = height band: what _set_gates last set), "held_height" / "refused_letterbox"
  * (features of the last frame the height band held / whose projection the letterbox refused); "cost_mode" (FLAME_HIP_FE_COST_*:
  * what _set_cost last set); "gain_invariant" (what _set_gain_invariant last set); "ref_grad" (1 while the gate of _set_ref_grad is on), "fail_ref_grad" (features of the last frame with
- * status REF_GRAD) */
+ * status REF_GRAD); "warp" (what _set_warp last set), "warp_refused" (features of the last frame the warped window refused) */
 int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value);
 /* Debug/test hook: every slot's state (max_features entries each; any pointer may be NULL): alive, reference pixel (u, v),
  * ring slot of its pose frame, prior (mu, var) in the pose frame, dropout counter, last status (-1 = free), last best sample. */
@@ -697,6 +697,37 @@ int flame_hip_frontend_set_gain_invariant(flame_hip_frontend* fe, int32_t on);
  * change in mid-sequence.  Valid on a handle without a device.  Errors: NAN (non-finite), ARG (NULL fe, negative); after a refusal
  * the setting is what it was.  Info keys "ref_grad", "fail_ref_grad". */
 int flame_hip_frontend_set_ref_grad(flame_hip_frontend* fe, float min_grad);
+
+/* ---- warped window (opt-in): the tracker compares the reference window with an axis-aligned, unscaled window of the current
+ * image, which is right only while the camera has neither rolled nor changed its distance against the pose frame: at 30 degrees of
+ * roll nearly every feature is lost.  With on = 1 the current image is sampled where the reference window's pixels
+ * land under the pose change, an affine 2 x 2 map J formed once per feature and frame from the pose record and the prior
+ * (DESIGN.md 5.3 "Warped window"; restated in tests/fe_warp_ref.py, which the GPU equals bit for bit).  Float32, every operation
+ * rounded on its own, no fused multiply-add; with a = A b, c, the clamped interval [xi0, xi1] and d0, d1 > 0 of the search:
+ *   xi_J = min(max(mu, xi0), xi1) (t = mu > xi0 ? mu : xi0; xi_J = t < xi1 ? t : xi1);  w_r = a_r + xi_J c_r;  px = w0 / w2,
+ *   py = w1 / w2;  gx_r = A[r][0] / fx,  gy_r = A[r][1] / fy  (r = 0, 1, 2: the derivatives of a by the reference pixel);
+ *   J00 = (gx0 - px gx2) / w2,  J01 = (gy0 - px gy2) / w2,  J10 = (gx1 - py gx2) / w2,  J11 = (gy1 - py gy2) / w2.
+ *   Jq = (int)floorf(J 256 + 0.5f) per entry, taken only when that float is finite and at most 1024 in magnitude (a stretch of 4),
+ *   and det = Jq00 Jq11 - Jq01 Jq10 >= 4096 (an area scale of 1/16; no mirrored, no collapsed map).
+ * A feature whose Jq fails either test is REFUSED before the search -- after the tests for OUTSIDE, NO_PARALLAX and REF_GRAD --:
+ * status OUTSIDE, one dropout, prior and k* = -1 untouched, search record zero (the Matches image draws nothing), counted in info
+ * key "warp_refused" (and in "outside").
+ * Cost of sample k: q = (int)floorf(p_k 16 + 0.5f) per axis with the range test as before; for the window offset (i, j), i along x
+ * and j along y, both in [-r, r]:
+ *   ox = qx + ((Jq00 i + Jq01 j + 8) >> 4),  oy = qy + ((Jq10 i + Jq11 j + 8) >> 4)   (arithmetic shifts: they floor; sixteenths);
+ *   I_ij = the 256-scaled bilinear sum of the current image at pixel (ox >> 4, oy >> 4) with the weights of ox & 15, oy & 15;
+ *   the sample is valid only if every window pixel and its +1 neighbours lie inside the image;
+ *   D_ij = I_ij - 256 ref(u + i, v + j) feeds SSD and ZSSD, I_ij the gain-invariant sums: their integer bounds hold unchanged.
+ * The reference side, the gradient gate and everything behind the cost (argmin, BAD_MATCH, AMBIGUOUS, parabola, measurement,
+ * fusion, projection, gates) are untouched.  Jq = (256, 0, 0, 256) gives the unwarped integers, and a pose change with R = I and
+ * t_z = 0 gives exactly that Jq: on such a sequence the switch changes no bit.  A quarter turn Jq = (0, -256, 256, 0) permutes the
+ * sampling positions: the cost on an image equals the unwarped cost on that image turned by 90 degrees about the sample.
+ * NOT claimed: J is taken at the prior, not per sample (for a wide prior the window's scale is that of xi_J); the patch's plane is
+ * taken as fronto-parallel in the pose frame, as the search itself assumes.
+ * Takes effect with the next _track / _track_raw and may change in mid-sequence (the feature state holds nothing of it).  Valid on
+ * a handle without a device.  Errors: ARG (NULL fe, on outside {0, 1}); the setting then stays what it was.  Info keys "warp",
+ * "warp_refused". */
+int flame_hip_frontend_set_warp(flame_hip_frontend* fe, int32_t on);
 
 /* Debug/test hook (no device needed; works on a handle created with device = -1): copies the
  * named host-side plan array ("v_o2i", "e_o2i", "grow", "ginc", "eij", "tiles", "t_vmap",

@@ -47,6 +47,9 @@
 // --min-epipolar-grad G (needs --gpu-frontend): Params::min_epipolar_grad -- the tracker's reference-patch gradient gate
 // (flame_hip_frontend_set_ref_grad): a feature whose reference window has a root-mean-square gradient below G along its epipolar
 // line is not searched.  The frame line ends with `fail_ref_grad <n>`, the stat key num_fail_ref_patch_grad of the frame.
+// --warp-window (needs --gpu-frontend): Params::warp_matching_window -- the tracker samples the current image where the reference
+// window's pixels land under the pose change (flame_hip_frontend_set_warp): for cameras that roll or change their distance.  The
+// frame line ends with `fail_warp <n>`, the stat key num_fail_warp of the frame.
 // --dump dir: frame_<id>.bin = {int32 V, T; float pos[2V], idepth_mu[V], idepth_var[V]; int32 tris[3T]; float idepth[V]}:
 // what went into the regulariser and what came out, for a bit-for-bit comparison with the oracle (tests).
 #include <cmath>
@@ -217,6 +220,8 @@ struct Lite {
       if (gpu && gpu->handle()) flame_hip_frontend_info(gpu->handle(), "gain_invariant", &on);
       std::printf(" gain_invariant %d", static_cast<int>(on));
     }
+    if (params.warp_matching_window)  // (appended at the end: without the flag the line is what it was)
+      std::printf(" fail_warp %d", st.stats().count("num_fail_warp") ? static_cast<int>(st.stats("num_fail_warp")) : -1);
     std::printf("\n");
   }
 };
@@ -236,6 +241,7 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[k], "--debug-images") && k + 1 < argc) L.debug_dir = argv[++k];
     else if (!std::strcmp(argv[k], "--zero-mean")) L.params.zero_mean_matching = true;
     else if (!std::strcmp(argv[k], "--gain-invariant")) L.params.gain_invariant_matching = true;
+    else if (!std::strcmp(argv[k], "--warp-window")) L.params.warp_matching_window = true;
     else if (!std::strcmp(argv[k], "--win-size") && k + 1 < argc) { L.params.zparams.win_size = std::atoi(argv[++k]); win_flag = true; }
     else if (!std::strcmp(argv[k], "--min-epipolar-grad") && k + 1 < argc) { L.params.min_epipolar_grad = static_cast<float>(std::atof(argv[++k])); rg_flag = true; }
     else if (!std::strcmp(argv[k], "--letterbox")) { L.params.do_letterbox = true; L.gates = true; }
@@ -250,13 +256,14 @@ int main(int argc, char** argv) {
   const bool asl = !args.empty() && !std::strcmp(args[0], "asl");
   if (!args.empty() && (!std::strcmp(args[0], "tum") || asl)) args.erase(args.begin());
   const bool bad_flags = (!L.debug_dir.empty() && !L.gpu_frontend) || (!L.dump_dir.empty() && L.gpu_frontend) ||
-                         ((L.gates || L.have_up || L.params.zero_mean_matching || L.params.gain_invariant_matching || win_flag || rg_flag) && !L.gpu_frontend) || bad_up;
+                         ((L.gates || L.have_up || L.params.zero_mean_matching || L.params.gain_invariant_matching || L.params.warp_matching_window || win_flag || rg_flag) && !L.gpu_frontend) || bad_up;
   if (bad_flags || (asl && args.size() < 4) || (!asl && args.size() < 6)) {
     std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-frontend [--debug-images dir]]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-rectify] [--gpu-frontend [--debug-images dir]]\n"
                  "  --gpu-frontend: features from the GPU tracker (not with --dump); --debug-images dir: detections_<id>.ppm / matches_<id>.ppm per frame (needs --gpu-frontend)\n"
                  "  --letterbox, --min-height H, --max-height H, --up-axis x,y,z (need --gpu-frontend): features only in the middle third of the rows / only inside the height band along the up axis (default 0,-1,0)\n"
                  "  --zero-mean (needs --gpu-frontend): match with the zero-mean SSD, which a grey offset between frames cannot move (auto-exposure cameras); --win-size N: the matching window (odd, <= 9)\n"
                  "  --gain-invariant (needs --gpu-frontend): match with the gain-invariant cost, which an exposure step between frames cannot move; overrides --zero-mean\n"
+                 "  --warp-window (needs --gpu-frontend): sample the current image where the reference window lands under the pose change (cameras that roll or change their distance)\n"
                  "  --min-epipolar-grad G (needs --gpu-frontend): do not search a feature whose reference window has a gradient below G along its epipolar line (0 = off)\n",
                  argv[0], argv[0]);
     return 2;

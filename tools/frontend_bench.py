@@ -19,10 +19,14 @@ their median and their spread -- what DESIGN.md 6 compares between two trees.  -
 --gain-invariant: the same pairs with the gain-invariant matching cost (GpuFrontEnd.set_gain_invariant: the third cost of
 k_fe_track -- three integer sums per window pixel and a double multiply, divide and subtract per sample).
 
+--warp: the same pairs with the warped matching window (GpuFrontEnd.set_warp: the warped instantiation of k_fe_track -- four byte
+loads instead of two and two integer multiply-adds per window pixel; under this sequence's sideways translation the map is the
+identity and the features are the same bits).
+
 --min-epipolar-grad G: the same pairs with the reference-patch gradient gate (GpuFrontEnd.set_ref_grad: the gated instantiation of
 k_fe_track -- 2 x 3 byte loads per lane and three wave sums in front of every search; a refused feature skips its search).
 
-    python tools/frontend_bench.py [--frames 100] [--warmup 10] [--gates] [--zero-mean] [--gain-invariant] [--win-size 7] [--min-epipolar-grad 5] [--repeat 5]
+    python tools/frontend_bench.py [--frames 100] [--warmup 10] [--gates] [--zero-mean] [--gain-invariant] [--warp] [--win-size 7] [--min-epipolar-grad 5] [--repeat 5]
 """
 import argparse
 import json
@@ -47,7 +51,7 @@ def texture(h, w, seed=5, factor=8):
     return np.floor(up + 0.5).astype(np.uint8)
 
 
-def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=False, win_size=5, min_epipolar_grad=0.0, gain_invariant=False):
+def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=False, win_size=5, min_epipolar_grad=0.0, gain_invariant=False, warp=False):
     from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
     K = np.array([525, 0, 319.5, 0, 525, 239.5, 0, 0, 1], np.float32)
     big = texture(H, W + shift)
@@ -65,6 +69,8 @@ def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=Fal
             fe.set_cost(zero_mean=True)
         if gain_invariant:
             fe.set_gain_invariant(True)
+        if warp:
+            fe.set_warp(True)
         if min_epipolar_grad > 0:
             fe.set_ref_grad(min_epipolar_grad)
         for i in range(warmup + frames):
@@ -83,6 +89,8 @@ def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=Fal
         res.update(cost_mode=1)
     if gain_invariant:
         res.update(gain_invariant=1)
+    if warp:
+        res.update(warp=1)
     if min_epipolar_grad > 0:
         res.update(min_epipolar_grad=min_epipolar_grad, fail_ref_grad=fail_rg)
     if win_size != 5:
@@ -100,11 +108,12 @@ if __name__ == "__main__":
     ap.add_argument("--gates", action="store_true")
     ap.add_argument("--zero-mean", action="store_true")
     ap.add_argument("--gain-invariant", action="store_true")
+    ap.add_argument("--warp", action="store_true")
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--win-size", type=int, default=5)
     ap.add_argument("--min-epipolar-grad", type=float, default=0.0)
     a = ap.parse_args()
-    runs = [run(max(a.frames, 50), a.warmup, gates=a.gates, zero_mean=a.zero_mean, win_size=a.win_size, min_epipolar_grad=a.min_epipolar_grad, gain_invariant=a.gain_invariant) for _ in range(max(a.repeat, 1))]
+    runs = [run(max(a.frames, 50), a.warmup, gates=a.gates, zero_mean=a.zero_mean, win_size=a.win_size, min_epipolar_grad=a.min_epipolar_grad, gain_invariant=a.gain_invariant, warp=a.warp) for _ in range(max(a.repeat, 1))]
     res = runs[-1]
     if a.repeat > 1:
         t = [r["tracking_device_us"] for r in runs]
