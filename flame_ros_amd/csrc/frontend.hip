@@ -36,54 +36,66 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 }
 __device__ __forceinline__ bool fe_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }
 
-// Cost of one sample: sum over the win x win window of (bilinear(cur, p) * 256 - 256 * ref)^2 with p quantised to 1/16 px;
-// kNone when the window (with its +1 bilinear neighbours) leaves the image.  Per row two running pixels are carried, so a
-// window pixel costs two loads of the current image and one of the reference patch.
-// ZM (DESIGN.md 5.3 "Matching cost", mode ZSSD): with D_i the n = win^2 differences, S1 = sum D_i (|S1| <= 81 * 65 280: an int32)
-// and S2 = sum D_i^2, the cost is n S2 - S1^2 -- n^2 times the variance of D over the window, >= 0, <= (n^2 - 1) 65 280^2 < 2^45,
-// and the same integer whatever constant a frame's exposure adds to every D_i.
-template <bool ZM>
-__device__ __forceinline__ unsigned long long fe_cost(const FeFrame& f, const uint8_t* __restrict__ ref, int u, int v, float px,
-                                                      float py) {
+// Position of one sample in sixteenths of a pixel, the quantisation every sampler shares; false when it lies outside the image
+// (the callers return at once then and never read the two integers: the test comes last so that they compile as they did inline).
+__device__ __forceinline__ bool fe_sample_q(const FeFrame& f, float px, float py, int* qx, int* qy) {
   const float fqx = floorf(px * 16.0f + 0.5f), fqy = floorf(py * 16.0f + 0.5f);
-  if (!(fqx >= 0.0f && fqx <= (float)(16 * f.W) && fqy >= 0.0f && fqy <= (float)(16 * f.H))) return kNone;
-  const int qx = (int)fqx, qy = (int)fqy;
-  const int ix = qx >> 4, iy = qy >> 4;
-  const int r = f.win >> 1;
-  if (ix - r < 0 || iy - r < 0 || ix + r + 1 > f.W - 1 || iy + r + 1 > f.H - 1) return kNone;
-  const int wx1 = qx & 15, wx0 = 16 - wx1, wy1 = qy & 15, wy0 = 16 - wy1;
-  unsigned long long C = 0;
-  int S1 = 0;
-  for (int dy = -r; dy <= r; ++dy) {
-    const uint8_t* __restrict__ r0 = f.cur + (size_t)(iy + dy) * f.W + (ix - r);
-    const uint8_t* __restrict__ r1 = r0 + f.W;
-    const uint8_t* __restrict__ rr = ref + (size_t)(v + dy) * f.W + (u - r);
-    int t0 = r0[0], b0 = r1[0];
-    for (int dx = 0; dx < f.win; ++dx) {
-      const int t1 = r0[dx + 1], b1 = r1[dx + 1];
-      const int D = wy0 * (wx0 * t0 + wx1 * t1) + wy1 * (wx0 * b0 + wx1 * b1) - 256 * (int)rr[dx];
-      const unsigned int aD = (unsigned int)(D < 0 ? -D : D);  // <= 65 280: the square fits 32 bits
-      C += (unsigned long long)(aD * aD);
-      if (ZM) S1 += D;
-      t0 = t1;
-      b0 = b1;
-    }
-  }
-  if (ZM) {
-    const unsigned int a1 = (unsigned int)(S1 < 0 ? -S1 : S1);
-    C = (unsigned long long)(unsigned int)(f.win * f.win) * C - (unsigned long long)a1 * (unsigned long long)a1;
-  }
-  return C;
+  *qx = (int)fqx;
+  *qy = (int)fqy;
+  return fqx >= 0.0f && fqx <= (float)(16 * f.W) && fqy >= 0.0f && fqy <= (float)(16 * f.H);
 }
 
+// The three matching costs of a window, stated once for the upright and the warped sampler.  add(I, R) takes one window pixel:
+// I = the bilinear sum of the current image, 256-scaled (0 ... 65 280), R = 256 ref (0 ... 65 280); cost() closes the sums.
+// SSD: the sum of D_i^2 over the n = win^2 differences D_i = I_i - R_i (|D| <= 65 280: the square fits 32 bits).
+// ZSSD (DESIGN.md 5.3 "Matching cost", mode ZSSD): with S1 = sum D_i (|S1| <= 81 * 65 280: an int32) and S2 = sum D_i^2, the cost
+// is n S2 - S1^2 -- n^2 times the variance of D over the window, >= 0, <= (n^2 - 1) 65 280^2 < 2^45, and the same integer whatever
+// constant a frame's exposure adds to every D_i.
 // The gain-invariant cost (DESIGN.md 5.3 "Matching cost", flame_hip_frontend_set_gain_invariant): the residual of the reference
-// window after the best fit ref ~ g cur + b.  With I_i the bilinear sum of the current image (0 ... 65 280) and R_i = 256 ref_i
-// over the n = win^2 window pixels, SI = sum I (< 2^23), SII = sum I^2, SIR = sum I R (each term < 2^32, the sums < 2^39) and
+// window after the best fit ref ~ g cur + b.  SI = sum I (< 2^23), SII = sum I^2, SIR = sum I R (each term < 2^32, the sums < 2^39)
+// and
 //   ZI = n SII - SI^2 (>= 0, < 2^45),  ZIR = n SIR - SI SR (signed, |ZIR| < 2^45),  ZR = n SRR - SR^2 (>= 0, < 2^45)
 // are exact integers; ZI == 0 (a flat current window) or ZIR <= 0 (anti-correlation is refused) leaves C = ZR, otherwise
 //   C = floor(ZR - ZIR^2 / ZI), clamped at 0:
 // a double multiply, divide and subtract on integers below 2^53, each rounded once (-ffp-contract=off) -- the bits of NumPy's
 // float64.  C <= ZR < 2^45: the argmin key keeps its width.  The unit is ZSSD's (n^2 x a variance in 256-scaled grey levels).
+template <int COST>
+struct FeSums {
+  unsigned long long S2 = 0, SIR = 0;  // sum D^2 (SSD, ZSSD) or sum I^2 (GI); sum I R (GI)
+  int S1 = 0;                          // sum D (ZSSD) or sum I (GI)
+  __device__ __forceinline__ void add(int I, int R) {
+    if constexpr (COST == kFeCostGi) {
+      S1 += I;
+      S2 += (unsigned long long)((unsigned int)I * (unsigned int)I);  // (both products fit 32 bits)
+      SIR += (unsigned long long)((unsigned int)I * (unsigned int)R);
+    } else {
+      const int D = I - R;
+      const unsigned int aD = (unsigned int)(D < 0 ? -D : D);
+      S2 += (unsigned long long)(aD * aD);
+      if (COST == kFeCostZssd) S1 += D;
+    }
+  }
+  // (SR, ZR): fe_ref_sums of the feature; the gain-invariant cost alone reads them
+  __device__ __forceinline__ unsigned long long cost(int win, unsigned int SR, unsigned long long ZR) const {
+    const unsigned long long n = (unsigned long long)(unsigned int)(win * win);
+    if constexpr (COST == kFeCostGi) {
+      const unsigned long long SI = (unsigned long long)(unsigned int)S1;
+      const unsigned long long ZI = n * S2 - SI * SI;
+      const long long ZIR = (long long)(n * SIR) - (long long)(SI * (unsigned long long)SR);
+      if (ZI == 0ull || ZIR <= 0ll) return ZR;
+      const double z = (double)ZIR;
+      const double q = (z * z) / (double)ZI;
+      const double Cd = (double)ZR - q;
+      return Cd > 0.0 ? (unsigned long long)floor(Cd) : 0ull;
+    } else if constexpr (COST == kFeCostZssd) {
+      const unsigned int a1 = (unsigned int)(S1 < 0 ? -S1 : S1);
+      return n * S2 - (unsigned long long)a1 * (unsigned long long)a1;
+    } else {
+      return S2;
+    }
+  }
+};
+
 // fe_ref_sums forms (SR, ZR) of the feature once, before the search: the 64 lanes cover the n <= 81 reference pixels in two
 // passes, s1 = sum ref <= 81 * 255 and s2 = sum ref^2 <= 81 * 255^2 < 2^23 are int32 sums an xor butterfly leaves in every lane
 // (any order: the same integers), SR = 256 s1 and ZR = 65536 (n s2 - s1^2).  The caller has tested that the window lies inside.
@@ -110,17 +122,19 @@ __device__ __forceinline__ void fe_ref_sums(const FeFrame& f, const uint8_t* __r
   *ZR = (unsigned long long)((unsigned int)n * t2 - t1 * t1) << 16;
 }
 
-__device__ __forceinline__ unsigned long long fe_cost_gi(const FeFrame& f, const uint8_t* __restrict__ ref, int u, int v, float px,
-                                                         float py, unsigned int SR, unsigned long long ZR) {
-  const float fqx = floorf(px * 16.0f + 0.5f), fqy = floorf(py * 16.0f + 0.5f);
-  if (!(fqx >= 0.0f && fqx <= (float)(16 * f.W) && fqy >= 0.0f && fqy <= (float)(16 * f.H))) return kNone;
-  const int qx = (int)fqx, qy = (int)fqy;
+// Cost of one sample on the upright window: the win x win bilinear window of the current image at p, quantised to 1/16 px, against
+// the reference window under the cost COST; kNone when the window (with its +1 bilinear neighbours) leaves the image.  Per row
+// two running pixels are carried, so a window pixel costs two loads of the current image and one of the reference patch.
+template <int COST>
+__device__ __forceinline__ unsigned long long fe_cost(const FeFrame& f, const uint8_t* __restrict__ ref, int u, int v, float px,
+                                                      float py, unsigned int SR, unsigned long long ZR) {
+  int qx, qy;
+  if (!fe_sample_q(f, px, py, &qx, &qy)) return kNone;
   const int ix = qx >> 4, iy = qy >> 4;
   const int r = f.win >> 1;
   if (ix - r < 0 || iy - r < 0 || ix + r + 1 > f.W - 1 || iy + r + 1 > f.H - 1) return kNone;
   const int wx1 = qx & 15, wx0 = 16 - wx1, wy1 = qy & 15, wy0 = 16 - wy1;
-  unsigned long long SII = 0, SIR = 0;
-  unsigned int SI = 0;
+  FeSums<COST> s;
   for (int dy = -r; dy <= r; ++dy) {
     const uint8_t* __restrict__ r0 = f.cur + (size_t)(iy + dy) * f.W + (ix - r);
     const uint8_t* __restrict__ r1 = r0 + f.W;
@@ -128,23 +142,12 @@ __device__ __forceinline__ unsigned long long fe_cost_gi(const FeFrame& f, const
     int t0 = r0[0], b0 = r1[0];
     for (int dx = 0; dx < f.win; ++dx) {
       const int t1 = r0[dx + 1], b1 = r1[dx + 1];
-      const unsigned int I = (unsigned int)(wy0 * (wx0 * t0 + wx1 * t1) + wy1 * (wx0 * b0 + wx1 * b1));  // <= 65 280
-      const unsigned int R = 256u * (unsigned int)rr[dx];                                                   // <= 65 280
-      SI += I;
-      SII += (unsigned long long)(I * I);  // (both products fit 32 bits)
-      SIR += (unsigned long long)(I * R);
+      s.add(wy0 * (wx0 * t0 + wx1 * t1) + wy1 * (wx0 * b0 + wx1 * b1), 256 * (int)rr[dx]);
       t0 = t1;
       b0 = b1;
     }
   }
-  const unsigned long long n = (unsigned long long)(unsigned int)(f.win * f.win);
-  const unsigned long long ZI = n * SII - (unsigned long long)SI * (unsigned long long)SI;
-  const long long ZIR = (long long)(n * SIR) - (long long)((unsigned long long)SI * (unsigned long long)SR);
-  if (ZI == 0ull || ZIR <= 0ll) return ZR;
-  const double z = (double)ZIR;
-  const double q = (z * z) / (double)ZI;
-  const double Cd = (double)ZR - q;
-  return Cd > 0.0 ? (unsigned long long)floor(Cd) : 0ull;
+  return s.cost(f.win, SR, ZR);
 }
 
 // The warped window (DESIGN.md 5.3 "Warped window", flame_hip_frontend_set_warp): the current image is sampled where the reference
@@ -182,14 +185,13 @@ __device__ __forceinline__ bool fe_warp_jq(const FeFrame& f, const FePose& P, fl
 // with the current image at (qx, qy) + ((Jq (i, j) + 8) >> 4) sixteenths of a pixel (an arithmetic shift: it floors), bilinear
 // with that position's own sixteenths -- four byte loads per window pixel.  The offsets are floors of a map linear in i and in j,
 // so their extremes over the window sit at its four corners: testing the corners (and their +1 neighbours) tests every pixel.
-// Jq = (256, 0, 0, 256) gives ox = qx + 16 i: the unwarped integers.  I feeds the sums of the cost COST exactly as in fe_cost /
-// fe_cost_gi, whose bounds hold unchanged (I <= 65 280).
+// Jq = (256, 0, 0, 256) gives ox = qx + 16 i: the unwarped integers.  I feeds FeSums<COST> exactly as in fe_cost: its bounds
+// hold unchanged (I <= 65 280).
 template <int COST>
 __device__ __forceinline__ unsigned long long fe_cost_warp(const FeFrame& f, const uint8_t* __restrict__ ref, int u, int v, float px,
                                                            float py, const FeJq& Jq, unsigned int SR, unsigned long long ZR) {
-  const float fqx = floorf(px * 16.0f + 0.5f), fqy = floorf(py * 16.0f + 0.5f);
-  if (!(fqx >= 0.0f && fqx <= (float)(16 * f.W) && fqy >= 0.0f && fqy <= (float)(16 * f.H))) return kNone;
-  const int qx = (int)fqx, qy = (int)fqy;
+  int qx, qy;
+  if (!fe_sample_q(f, px, py, &qx, &qy)) return kNone;
   const int r = f.win >> 1;
 #pragma unroll
   for (int corner = 0; corner < 4; ++corner) {
@@ -197,8 +199,7 @@ __device__ __forceinline__ unsigned long long fe_cost_warp(const FeFrame& f, con
     const int x = (qx + ((Jq.j00 * i + Jq.j01 * j + 8) >> 4)) >> 4, y = (qy + ((Jq.j10 * i + Jq.j11 * j + 8) >> 4)) >> 4;
     if (x < 0 || y < 0 || x + 1 > f.W - 1 || y + 1 > f.H - 1) return kNone;
   }
-  unsigned long long S2 = 0, SIR = 0;  // sum D^2 (SSD, ZSSD) or sum I^2 (GI); sum I R (GI)
-  int S1 = 0;                          // sum D (ZSSD) or sum I (GI)
+  FeSums<COST> s;
   for (int j = -r; j <= r; ++j) {
     const uint8_t* __restrict__ rr = ref + (size_t)(v + j) * f.W + u;
     for (int i = -r; i <= r; ++i) {
@@ -206,35 +207,10 @@ __device__ __forceinline__ unsigned long long fe_cost_warp(const FeFrame& f, con
       const uint8_t* __restrict__ q = f.cur + (size_t)(oy >> 4) * f.W + (ox >> 4);
       const int wx1 = ox & 15, wx0 = 16 - wx1, wy1 = oy & 15, wy0 = 16 - wy1;
       const int I = wy0 * (wx0 * (int)q[0] + wx1 * (int)q[1]) + wy1 * (wx0 * (int)q[f.W] + wx1 * (int)q[f.W + 1]);  // <= 65 280
-      const int R = 256 * (int)rr[i];
-      if constexpr (COST == kFeCostGi) {
-        S1 += I;
-        S2 += (unsigned long long)((unsigned int)I * (unsigned int)I);  // (both products fit 32 bits)
-        SIR += (unsigned long long)((unsigned int)I * (unsigned int)R);
-      } else {
-        const int D = I - R;
-        const unsigned int aD = (unsigned int)(D < 0 ? -D : D);
-        S2 += (unsigned long long)(aD * aD);
-        if (COST == kFeCostZssd) S1 += D;
-      }
+      s.add(I, 256 * (int)rr[i]);
     }
   }
-  const unsigned long long n = (unsigned long long)(unsigned int)(f.win * f.win);
-  if constexpr (COST == kFeCostGi) {
-    const unsigned long long SI = (unsigned long long)(unsigned int)S1;
-    const unsigned long long ZI = n * S2 - SI * SI;
-    const long long ZIR = (long long)(n * SIR) - (long long)(SI * (unsigned long long)SR);
-    if (ZI == 0ull || ZIR <= 0ll) return ZR;
-    const double z = (double)ZIR;
-    const double q = (z * z) / (double)ZI;
-    const double Cd = (double)ZR - q;
-    return Cd > 0.0 ? (unsigned long long)floor(Cd) : 0ull;
-  } else if constexpr (COST == kFeCostZssd) {
-    const unsigned int a1 = (unsigned int)(S1 < 0 ? -S1 : S1);
-    return n * S2 - (unsigned long long)a1 * (unsigned long long)a1;
-  } else {
-    return S2;
-  }
+  return s.cost(f.win, SR, ZR);
 }
 
 // The reference-patch gradient gate (DESIGN.md 5.3 "Reference-patch gradient"): does the win x win reference window have structure
@@ -356,8 +332,7 @@ __global__ __launch_bounds__(256) void k_fe_track(FeFrame f) {
         unsigned long long c = kNone;
         if (64 * pass <= S && k <= S) {
           if constexpr (WARP) c = fe_cost_warp<COST>(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey, Jq, SR, ZR);
-          else if constexpr (COST == kFeCostGi) c = fe_cost_gi(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey, SR, ZR);
-          else c = fe_cost<COST == kFeCostZssd>(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey);
+          else c = fe_cost<COST>(f, ref, u, v, x0 + (float)k * ex, y0 + (float)k * ey, SR, ZR);
         }
         C[pass] = c;
         if (c != kNone) {  // (c < 2^39 -- ZSSD, GI: c < 2^45 --, k < 2^9: one 64-bit key < 2^54 orders by cost, then by k)

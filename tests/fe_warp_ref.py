@@ -1,26 +1,18 @@
 """The feature front end's warped matching window (DESIGN.md 5.3 "Warped window"; include/flame_hip.h, flame_hip_frontend_set_warp)
-restated in NumPy on top of tests/fe_gi_ref.py (and so of fe_zm_ref.py and frontend_ref.py).  A helper, not a test:
+restated in NumPy: the rules tests/frontend_ref.py's FrontEndRef applies after `set_warp`.  A helper, not a test:
 tests/test_fe_warp_ref.py checks it on hand-written windows, rule by rule, against float64 geometry and against ground truth,
 tests/test_gpu_fe_warp.py compares the library with it bit for bit.
 
-`WarpRef` is GiRef plus `set_warp`.  With the switch off every call goes to the base classes untouched.  With it on `_track_one`
-repeats the base class's tests up to NO_PARALLAX -- the same float32 operations in the same order -- and, for a feature that
-would now be searched, forms
+With the switch on a feature that has passed the NO_PARALLAX test (and the gradient gate, which is tested first) forms
   * xi_J = the prior clamped into the searched interval, w = a + xi_J c, (px, py) = (w0, w1) / w2,
   * J = ((gx0 - px gx2, gy0 - px gy2), (gx1 - py gx2, gy1 - py gy2)) / w2 with gx_r = A[r][0] / fx, gy_r = A[r][1] / fy,
   * Jq = floor(256 J + 0.5) per entry, refused unless that float is finite and at most 1024 in magnitude, and unless
     det Jq >= 4096.
-A refused feature takes the base class's failure path with status OUTSIDE and no search, and is counted in
-counts["warp_refused"].  Otherwise the base class (whichever follows in the MRO: the SSD, ZSSD or gain-invariant search) runs the
-search, and every cost it asks for is `warped_windows` under that cost's own integer rule -- restated here, the base classes'
-`_cost` are not touched.  The combined classes put the gradient gate in FRONT of this class (it is tested first) and the gates and
-the search record around both."""
+A refused feature fails with status OUTSIDE and no search, and is counted in counts["warp_refused"].  Otherwise the search runs and
+every cost it asks for is `warped_windows` under the cost's own integer rule (`warped_cost`)."""
 import numpy as np
 
-from tests import fe_debug_ref as D
-from tests import fe_gates_ref as G
 from tests import fe_gi_ref as GI
-from tests import fe_rg_ref as RG
 from tests import fe_zm_ref as Z
 from tests import frontend_ref as R
 
@@ -85,131 +77,16 @@ def warped_windows(cur, ref, u, v, px, py, win, Jq, W, H):
 
 
 def warped_cost(Iw, Rw, cost):
-    """The three costs on the warped window: "ssd", "zssd", "gi"."""
+    """The three costs on a window (warped or upright): "ssd", "zssd", "gi"."""
     if cost == "gi":
         return GI.gi_cost(Iw, Rw)[0]
     Dm = Iw - Rw
     return Z.zssd(Dm) if cost == "zssd" else int(sum(int(x) * int(x) for x in Dm.reshape(-1)))
 
 
-class WarpRef(GI.GiRef):
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self.warp = False
-        self._Jq = None   # the map of the feature whose search is running
-        self.maps = []    # (slot, u, v, pose frame's T_world_ref, xi_J, J, Jq or None) of every map formed, for the tests
-
-    def set_warp(self, on=True):
-        self.warp = bool(on)
-
-    def cost_name(self):
-        return "gi" if self.gain_invariant else "zssd" if self.cost_mode == Z.COST_ZSSD else "ssd"
-
-    def _cost(self, cur, ref, u, v, px, py, win):
-        if self._Jq is None:
-            return super()._cost(cur, ref, u, v, px, py, win)
-        w = warped_windows(cur, ref, u, v, px, py, win, self._Jq, self.W, self.H)
-        return None if w is None else warped_cost(w[0], w[1], self.cost_name())
-
-    def _w_geometry(self, s, p, poses):
-        """FrontEndRef._track_one's tests before the search; (A, c, a, xi0, xi1) when the feature reaches it, else None."""
-        W, H, win = self.W, self.H, p["win_size"]
-        fx, fy, cx, cy = self.K4
-        u, v, f = int(self.u[s]), int(self.v[s]), int(self.pf[s])
-        mu, var = self.mu[s], self.var[s]
-        A, c = poses[f]
-        b0, b1 = (F(u) - cx) / fx, (F(v) - cy) / fy
-        a0 = (A[0][0] * b0 + A[0][1] * b1) + A[0][2]
-        a1 = (A[1][0] * b0 + A[1][1] * b1) + A[1][2]
-        a2 = (A[2][0] * b0 + A[2][1] * b1) + A[2][2]
-        c0, c1, c2 = c
-        two = F(2.0) * np.sqrt(var)
-        lo, hi = mu - two, mu + two
-        idmin, idmax = F(p["idepth_min"]), F(p["idepth_max"])
-        xi0 = lo if lo > idmin else idmin
-        xi1 = hi if hi < idmax else idmax
-        d0, d1 = a2 + xi0 * c2, a2 + xi1 * c2
-        r = win // 2
-        ref_in = u - r >= 0 and v - r >= 0 and u + r <= W - 1 and v + r <= H - 1
-        if not (d0 > 0 and d1 > 0) or not ref_in:
-            return None
-        x0, y0 = (a0 + xi0 * c0) / d0, (a1 + xi0 * c1) / d0
-        x1, y1 = (a0 + xi1 * c0) / d1, (a1 + xi1 * c1) / d1
-        dx, dy = x1 - x0, y1 - y0
-        L = np.sqrt(dx * dx + dy * dy)
-        if not (L >= F(2.0)):
-            return None
-        return A, c, (a0, a1, a2), xi0, xi1
-
-    def _w_refuse(self, s, p, a, c):
-        """FrontEndRef._track_one behind OUTSIDE without a search: prior and k* = -1 untouched, the projection of the prior, one
-        dropout, death past max_dropouts."""
-        W, H = self.W, self.H
-        mu, var, drop = self.mu[s], self.var[s], int(self.drop[s])
-        (a0, a1, a2), (c0, c1, c2) = a, c
-        w0, w1, w2 = a0 + mu * c0, a1 + mu * c1, a2 + mu * c2
-        pok, proj = False, None
-        if w2 > 0:
-            px, py, xc = w0 / w2, w1 / w2, mu / w2
-            g = a2 / (w2 * w2)
-            vc = var * (g * g)
-            pok = bool(px >= 0 and px <= F(W - 1) and py >= 0 and py <= F(H - 1) and np.isfinite(xc) and np.isfinite(vc) and vc >= 0)
-            proj = (px, py, xc, vc)
-        drop += 1
-        self.drop[s], self.kstar[s] = drop, -1
-        self.counts[R.OUTSIDE] = self.counts.get(R.OUTSIDE, 0) + 1
-        self.counts["warp_refused"] = self.counts.get("warp_refused", 0) + 1
-        if drop > p["max_dropouts"]:
-            self.alive[s], self.status[s] = 0, R.DIED
-            self.counts[R.DIED] = self.counts.get(R.DIED, 0) + 1
-            return None
-        self.status[s] = R.OUTSIDE
-        if not pok:
-            return None
-        dws = p["detection_win_size"]
-        ncx = (W + dws - 1) // dws
-        return (int(py) // dws) * ncx + int(px) // dws, proj
-
-    def _track_one(self, s, p, cur, poses):
-        g = self._w_geometry(s, p, poses) if self.warp else None
-        if g is None:
-            return super()._track_one(s, p, cur, poses)
-        A, c, a, xi0, xi1 = g
-        J = jacobian32(self.K4, A, c, a, self.mu[s], xi0, xi1)
-        Jq = quantise(J[:4])
-        self.maps.append((s, int(self.u[s]), int(self.v[s]), self.pf_T[int(self.pf[s])], J[4], J[:4], Jq))
-        if Jq is None:
-            return self._w_refuse(s, p, a, c)
-        self._Jq = Jq
-        try:
-            return super()._track_one(s, p, cur, poses)
-        finally:
-            self._Jq = None
-
-    def warp_refused(self):
-        """Of the last frame."""
-        return self.counts.get("warp_refused", 0)
-
-
-class WarpDebugRef(D.DebugRef, WarpRef):
-    """WarpRef with DebugRef's search record and pictures (a refused slot leaves steps = 0 and draws nothing)."""
-
-
-class WarpGatesDebugRef(D.DebugRef, G.GatesRef, WarpRef):
-    """... and GatesRef's gates between the two: they act on the projection the search left."""
-
-
-class RgWarpDebugRef(D.DebugRef, RG.RgRef, WarpRef):
-    """... the gradient gate in front of the warp test: REF_GRAD is decided first."""
-
-
-class RgWarpGatesDebugRef(D.DebugRef, RG.RgGatesRef, WarpRef):
-    """... and all of them."""
-
-
-def run(frames, W, H, K, warp=True, cost="ssd", poseframes=(0,), ref=None, **kw):
+def run(frames, W, H, K, warp=True, cost="ssd", poseframes=(0,), **kw):
     """The restatement over a scene; returns (ref, per-frame outputs)."""
-    fe = (ref or WarpRef)(W, H, K, 256, 4)
+    fe = R.FrontEndRef(W, H, K, 256, 4)
     fe.set_warp(warp)
     fe.set_cost(cost == "zssd")
     fe.set_gain_invariant(cost == "gi")

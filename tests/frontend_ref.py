@@ -1,8 +1,13 @@
 """The feature front end's algorithm statement (DESIGN.md "Feature front end") restated in NumPy: np.float32 scalars in
 the kernels' operation order (no fused multiply-add exists here), Python integers for the image costs.  The GPU
 (flame_ros_amd/csrc/frontend.hip behind flame_hip_frontend_*) must equal this BIT FOR BIT: slots, statuses, k*, mu, var and
-the emitted features.  tests/test_frontend_ref.py checks this file against ground truth, so that "GPU equals
+the emitted features, the search record.  tests/test_frontend_ref.py checks this file against ground truth, so that "GPU equals
 restatement" is not circular.  Also the synthetic scenes both test files use.
+
+FrontEndRef states the tracker once, with every opt-in switch where k_fe_track has it.  The rule of each switch is a pure
+function in the module whose tests pin it -- fe_zm_ref (ZSSD), fe_gi_ref (gain-invariant cost), fe_rg_ref (gradient gate),
+fe_warp_ref (warped window), fe_gates_ref (letterbox, height band), fe_debug_ref (debug images) -- and those modules read this
+one's constants and scenes, so they are imported at the foot of this file.
 """
 import math
 
@@ -65,8 +70,30 @@ def _finite(x):
     return bool(np.isfinite(x))
 
 
+def upright_windows(cur, ref, u, v, px, py, win, W, H):
+    """(I, R) of the sample at (px, py) on the upright window -- I the 256-scaled bilinear sums of `cur` at the sample quantised to
+    1/16 px, R = 256 x the reference window -- or None when the window (with its +1 bilinear neighbours) leaves the image."""
+    r = win // 2
+    with np.errstate(all="ignore"):
+        fqx, fqy = np.floor(px * F(16.0) + F(0.5)), np.floor(py * F(16.0) + F(0.5))
+    if not (fqx >= 0 and fqx <= F(16 * W) and fqy >= 0 and fqy <= F(16 * H)):
+        return None
+    qx, qy = int(fqx), int(fqy)
+    ix, iy = qx >> 4, qy >> 4
+    if ix - r < 0 or iy - r < 0 or ix + r + 1 > W - 1 or iy + r + 1 > H - 1:
+        return None
+    wx1, wy1 = qx & 15, qy & 15
+    wx0, wy0 = 16 - wx1, 16 - wy1
+    c = np.asarray(cur)[iy - r:iy + r + 2, ix - r:ix + r + 2].astype(np.int64)
+    Iw = (wx0 * wy0) * c[:-1, :-1] + (wx1 * wy0) * c[:-1, 1:] + (wx0 * wy1) * c[1:, :-1] + (wx1 * wy1) * c[1:, 1:]
+    return Iw, 256 * np.asarray(ref)[v - r:v + r + 1, u - r:u + r + 1].astype(np.int64)
+
+
 class FrontEndRef:
-    """Same calls and the same state as a flame_hip_frontend handle."""
+    """Same calls and the same state as a flame_hip_frontend handle, every switch included: `set_cost` (ZSSD), `set_gain_invariant`,
+    `set_warp`, `set_ref_grad`, `set_gates`.  `_track_one` is k_fe_track and `track` is the frame around it, each stated once, in the
+    kernels' order, with the switches where the kernels have them; the rule of every switch is a pure function of the module that
+    tests it (fe_zm_ref, fe_gi_ref, fe_rg_ref, fe_warp_ref, fe_gates_ref, fe_debug_ref: imported at the foot of this file)."""
 
     def __init__(self, W, H, K, max_features=2048, max_poseframes=8):
         K = np.asarray(K, np.float32).reshape(9)
@@ -83,27 +110,93 @@ class FrontEndRef:
         self.mu, self.var = np.zeros(n, np.float32), np.zeros(n, np.float32)
         self.status, self.kstar = np.full(n, FREE, np.int32), np.full(n, -1, np.int32)
         self.pstar = np.full((n, 2), np.nan, np.float32)  # matched position of the last OK frame (for the ground-truth tests)
-        self.steps = np.zeros(n, np.int32)                # S of the last search (for the tests' own sanity checks)
-        self.counts = {}
+        # the search record of the last frame: S and {x0, y0, ex, ey} of every slot that ran a search, else zero
+        self.steps, self.seg = np.zeros(n, np.int32), np.zeros((n, 4), np.float32)
+        self.image = None    # the image the last track() tracked
+        self.emitted = None  # what the last track() returned
+        self.counts = {}     # of the last frame: status -> features, "warp_refused" -> refused maps
+        self.dropped = 0
+        # ---- the switches ----
+        self.cost_mode = Z.COST_SSD
+        self.gain_invariant = False
+        self.warp = False
+        self.min_epi_grad = F(0.0)
+        self.gates = None    # dict(letterbox, height, min_height, max_height, up) or None
+        # ---- what the switches leave for the tests ----
+        self._Jq = None      # the map of the feature whose search is running
+        self.maps = []       # (slot, u, v, pose frame's T_world_ref, xi_J, J, Jq or None) of every map formed; the caller empties it
+        self._epi = []       # the frame's epipole per pose frame
+        self.decisions = []  # (slot, u, v, pose frame's T_world_ref, E, S, passed) of every gradient test of the frame
+        self._g = None       # the frame's gate record, None when no gate is set
+        self.held = self.refused = 0
+        self.held_slots = []
+        self._held_cells = set()
+        self.proj_all = {}   # slot -> (px, py, xc, vc) of every acceptable projection of the frame, before the gates (gated frames only)
 
-    # ---- one sample's cost ----
+    # ---- the switches ----
+    def set_cost(self, zero_mean=True):
+        self.cost_mode = Z.COST_ZSSD if zero_mean else Z.COST_SSD
+
+    def set_gain_invariant(self, on=True):
+        self.gain_invariant = bool(on)  # (does not touch cost_mode)
+
+    def set_warp(self, on=True):
+        self.warp = bool(on)
+
+    def set_ref_grad(self, min_grad):
+        g = F(min_grad)
+        if not np.isfinite(g):
+            raise ValueError("non-finite min_grad")
+        if g < 0:
+            raise ValueError("negative min_grad")
+        self.min_epi_grad = g
+
+    def set_gates(self, letterbox=False, min_height=None, max_height=None, up=(0, -1, 0)):
+        height = min_height is not None or max_height is not None
+        if not letterbox and not height:
+            self.gates = None
+            return
+        lo = F(-G.BIG if min_height is None else min_height)
+        hi = F(G.BIG if max_height is None else max_height)
+        if height:
+            vals = [lo, hi] + [F(a) for a in up]
+            if not all(np.isfinite(x) for x in vals):
+                raise ValueError("non-finite gate")
+            if lo > hi or not any(F(a) != 0 for a in up):
+                raise ValueError("empty band or zero up vector")
+        self.gates = dict(letterbox=bool(letterbox), height=height, min_height=lo, max_height=hi, up=tuple(up))
+
+    def cost_name(self):
+        return "gi" if self.gain_invariant else "zssd" if self.cost_mode == Z.COST_ZSSD else "ssd"
+
+    # ---- one sample's cost: the window (warped while a map is in force), then the cost's integer rule ----
+    def _windows(self, cur, ref, u, v, px, py, win):
+        return upright_windows(cur, ref, u, v, px, py, win, self.W, self.H)
+
     def _cost(self, cur, ref, u, v, px, py, win):
-        r = win // 2
-        fqx, fqy = np.floor(px * F(16.0) + F(0.5)), np.floor(py * F(16.0) + F(0.5))
-        if not (fqx >= 0 and fqx <= F(16 * self.W) and fqy >= 0 and fqy <= F(16 * self.H)):
-            return None
-        qx, qy = int(fqx), int(fqy)
-        ix, iy = qx >> 4, qy >> 4
-        if ix - r < 0 or iy - r < 0 or ix + r + 1 > self.W - 1 or iy + r + 1 > self.H - 1:
-            return None
-        wx1, wy1 = qx & 15, qy & 15
-        wx0, wy0 = 16 - wx1, 16 - wy1
-        c = cur[iy - r:iy + r + 2, ix - r:ix + r + 2]
-        D = (wx0 * wy0) * c[:-1, :-1] + (wx1 * wy0) * c[:-1, 1:] + (wx0 * wy1) * c[1:, :-1] + (wx1 * wy1) * c[1:, 1:] \
-            - 256 * ref[v - r:v + r + 1, u - r:u + r + 1]
-        return int((D * D).sum())
+        if self._Jq is None:
+            w = self._windows(cur, ref, u, v, px, py, win)
+        else:
+            w = WR.warped_windows(cur, ref, u, v, px, py, win, self._Jq, self.W, self.H)
+        return None if w is None else WR.warped_cost(w[0], w[1], self.cost_name())
 
-    # ---- track + project one live feature; returns (cell, proj) or None ----
+    # ---- the gradient gate of one feature: OK, REF_GRAD, or OUTSIDE when the window's one-pixel ring leaves the image ----
+    def _ref_grad(self, s, u, v, f, win):
+        St = RG.structure_tensor(self.pf_img[f], u, v, win)
+        if St is None:
+            return OUTSIDE
+        ok = RG.passes(self._epi[f], u, v, St, win, self.min_epi_grad)
+        self.decisions.append((s, u, v, self.pf_T[f], self._epi[f], St, ok))
+        return OK if ok else RG.REF_GRAD
+
+    # ---- the warp map of one feature: Jq, or None when it is refused ----
+    def _map(self, s, u, v, f, A, c, a, mu, xi0, xi1):
+        J = WR.jacobian32(self.K4, A, c, a, mu, xi0, xi1)
+        Jq = WR.quantise(J[:4])
+        self.maps.append((s, u, v, self.pf_T[f], J[4], J[:4], Jq))
+        return Jq
+
+    # ---- track + project one live feature (k_fe_track); returns (cell, proj) or None ----
     def _track_one(self, s, p, cur, poses):
         W, H, win = self.W, self.H, p["win_size"]
         fx, fy, cx, cy = self.K4
@@ -111,6 +204,8 @@ class FrontEndRef:
         mu, var, drop = self.mu[s], self.var[s], int(self.drop[s])
         A, c = poses[f]
         ref = self.pf_img[f]
+        cost = self.cost_name()
+        # 1. geometry
         b0, b1 = (F(u) - cx) / fx, (F(v) - cy) / fy
         a0 = (A[0][0] * b0 + A[0][1] * b1) + A[0][2]
         a1 = (A[1][0] * b0 + A[1][1] * b1) + A[1][2]
@@ -126,6 +221,7 @@ class FrontEndRef:
         ref_in = u - r >= 0 and v - r >= 0 and u + r <= W - 1 and v + r <= H - 1
         ks = -1
         mu_new, var_new = mu, var
+        # 2. OUTSIDE / NO_PARALLAX
         if not (d0 > 0 and d1 > 0) or not ref_in:
             status = OUTSIDE
         else:
@@ -133,21 +229,44 @@ class FrontEndRef:
             x1, y1 = (a0 + xi1 * c0) / d1, (a1 + xi1 * c1) / d1
             dx, dy = x1 - x0, y1 - y0
             L = np.sqrt(dx * dx + dy * dy)
+            rg, Jq = OK, None
             if not (L >= F(2.0)):
                 status = NO_PARALLAX
+            # 3. the gradient gate: no search, a failure
+            elif self.min_epi_grad > 0 and (rg := self._ref_grad(s, u, v, f, win)) != OK:
+                status = rg
+            # 4. the warp map; one out of range: no search, a failure
+            elif self.warp and (Jq := self._map(s, u, v, f, A, c, (a0, a1, a2), mu, xi0, xi1)) is None:
+                status = OUTSIDE
+                self.counts["warp_refused"] = self.counts.get("warp_refused", 0) + 1
             else:
+                # 5. the search
                 S = MAX_SAMPLES if L >= F(MAX_SAMPLES) else int(np.ceil(L))
                 ex, ey = dx / F(S), dy / F(S)
-                self.steps[s] = S
-                C = [self._cost(cur, ref, u, v, x0 + F(k) * ex, y0 + F(k) * ey, win) for k in range(S + 1)]
+                self.steps[s], self.seg[s] = S, (x0, y0, ex, ey)
+                ZR = 0
+                if cost == "gi":
+                    Rw = 256 * ref[v - r:v + r + 1, u - r:u + r + 1].astype(np.int64)
+                    ZR = GI.window_sums(Rw, Rw)[2]  # of the feature, not of the sample
+                self._Jq = Jq
+                try:
+                    C = [self._cost(cur, ref, u, v, x0 + F(k) * ex, y0 + F(k) * ey, win) for k in range(S + 1)]
+                finally:
+                    self._Jq = None
                 valid = [k for k in range(S + 1) if C[k] is not None]
+                # 6. argmin, BAD_MATCH, AMBIGUOUS, the parabola, the fusion
                 if not valid:
                     status = OUTSIDE
                 else:
-                    ks = min(valid, key=lambda k: (C[k], k))
+                    ks = min(valid, key=lambda k: (C[k], k))  # the key (C << 9) | k: smallest cost, then smallest k
                     Cb = C[ks]
-                    bad = int(float(F(p["max_match_error"])) * float(win * win) * 65536.0)
-                    if Cb > bad:
+                    if cost == "zssd":
+                        assert all(0 <= C[k] < 2 ** 45 for k in valid)
+                    if cost == "gi":
+                        assert all(0 <= C[k] <= ZR < 2 ** 45 for k in valid)
+                    if cost == "gi" and ZR == 0:
+                        status = BAD_MATCH  # a flat reference window: nothing to correlate
+                    elif Cb > Z.bad_threshold(p["max_match_error"], win, Z.COST_SSD if cost == "ssd" else Z.COST_ZSSD):
                         status = BAD_MATCH
                     elif any(abs(k - ks) > 2 and 2 * C[k] < 3 * Cb for k in valid):
                         status = AMBIGUOUS
@@ -156,7 +275,7 @@ class FrontEndRef:
                         Cp = C[ks + 1] if ks + 1 <= S else None
                         delta = F(0.0)
                         if Cm is not None and Cp is not None:
-                            fm, f0, fp = F(Cm), F(Cb), F(Cp)
+                            fm, f0, fp = F(Cm), F(Cb), F(Cp)  # (< 2^53: exact in the double NumPy goes through, rounded once)
                             den = (fm - F(2.0) * f0) + fp
                             if den > 0:
                                 delta = (F(0.5) * (fm - fp)) / den
@@ -182,9 +301,11 @@ class FrontEndRef:
                             self.pstar[s] = (xs, ys)
                         else:
                             status = BAD_MATCH
-        failed = status in (OUTSIDE, BAD_MATCH, AMBIGUOUS)
+        # 7. failed
+        failed = status in (OUTSIDE, BAD_MATCH, AMBIGUOUS, RG.REF_GRAD)
         if status == OK:
             mu, var, drop = mu_new, var_new, 0
+        # 8. projection into the current frame
         w0, w1, w2 = a0 + mu * c0, a1 + mu * c1, a2 + mu * c2
         pok, proj = False, None
         if w2 > 0:
@@ -193,6 +314,14 @@ class FrontEndRef:
             vc = var * (g * g)
             pok = bool(px >= 0 and px <= F(W - 1) and py >= 0 and py <= F(H - 1) and _finite(xc) and _finite(vc) and vc >= 0)
             proj = (px, py, xc, vc)
+        # 9. the letterbox: a projection outside the band of rows fails like one outside the image
+        gate = self._g
+        if gate is not None and pok:
+            self.proj_all[s] = proj
+            if not (py >= F(gate["y_lo"]) and py <= F(gate["y_hi"] - 1)):
+                self.refused += 1
+                pok = False
+        # 10. dropout and death
         if failed or not pok:
             drop += 1
         self.mu[s], self.var[s], self.drop[s], self.kstar[s] = mu, var, drop, ks
@@ -206,7 +335,17 @@ class FrontEndRef:
             return None
         dws = p["detection_win_size"]
         ncx = (W + dws - 1) // dws
-        return (int(py) // dws) * ncx + int(px) // dws, proj
+        cell = (int(py) // dws) * ncx + int(px) // dws
+        # 11. the height gate: a held feature keeps everything and is no candidate, its cell stays occupied
+        if gate is not None and gate["height"]:
+            h = G.height32(self.K4, gate["hr"], gate["h0"], px, py, xc)
+            if not (h >= gate["min_height"] and h <= gate["max_height"]):  # (a NaN height fails both)
+                self.held += 1
+                self.held_slots.append(s)
+                self._held_cells.add(cell)
+                return None
+        # 12. the cell
+        return cell, proj
 
     def track(self, p, img, img_id, T_world_cam, is_poseframe):
         W, H, win, dws = self.W, self.H, p["win_size"], p["detection_win_size"]
@@ -215,6 +354,23 @@ class FrontEndRef:
         cur = img.astype(np.int64)
         T = np.asarray(T_world_cam, np.float64).reshape(3, 4)
         self.counts = {}
+        self.steps[:] = 0
+        self.seg[:] = 0
+        self.decisions = []
+        self.held = self.refused = 0
+        self.held_slots = []
+        self._held_cells = set()
+        self.proj_all = {}
+        # the frame's gate record: the band of rows (the whole image without a letterbox) and the height gate's (hr, h0)
+        self._g, y_lo, y_hi = None, 0, H
+        if self.gates is not None:
+            gs = self.gates
+            if gs["letterbox"]:
+                G.check_band(H, win)
+                y_lo, y_hi = G.band(H)
+            self._g = dict(y_lo=y_lo, y_hi=y_hi, height=gs["height"], min_height=gs["min_height"], max_height=gs["max_height"])
+            if gs["height"]:
+                self._g["hr"], self._g["h0"] = G.gate_record(T, gs["up"])
         cur_pf = -1
         if is_poseframe:
             cur_pf = self.pf_added % self.P
@@ -226,6 +382,9 @@ class FrontEndRef:
         cell_key = {}
         cell_of, proj = {}, {}
         with np.errstate(all="ignore"):
+            self._epi = []
+            if self.min_epi_grad > 0:  # (the host forms the epipoles only for the gated kernel)
+                self._epi = [RG.epipole_record(self.K4, T, self.pf_T[q]) if self.pf_used[q] else None for q in range(self.P)]
             for s in range(self.F):
                 if not self.alive[s]:
                     self.status[s], self.kstar[s] = FREE, -1
@@ -243,11 +402,11 @@ class FrontEndRef:
             thr, m = g2_threshold(p["min_grad_mag"]), win // 2 + 1
             free = [s for s in range(self.F) if not self.alive[s]]
             for cell in range(ncx * ncy):
-                if cell in cell_key:
+                if cell in cell_key or cell in self._held_cells:  # occupied by an emitted feature, or by one the height gate holds
                     continue
                 ccx, ccy = cell % ncx, cell // ncx
                 xlo, xhi = max(ccx * dws, m), min(ccx * dws + dws, W - m)
-                ylo, yhi = max(ccy * dws, m), min(ccy * dws + dws, H - m)
+                ylo, yhi = max(ccy * dws, m, y_lo), min(ccy * dws + dws, H - m, y_hi)
                 if xhi <= xlo or yhi <= ylo:
                     continue
                 sub = g2[ylo:yhi, xlo:xhi]
@@ -263,15 +422,19 @@ class FrontEndRef:
                 self.alive[s], self.u[s], self.v[s], self.pf[s], self.drop[s] = 1, x, y, cur_pf, 0
                 self.mu[s], self.var[s] = F(p["idepth_init"]), F(p["var_init"])
                 self.status[s], self.kstar[s] = NEW, -1
+                self.steps[s], self.seg[s] = 0, 0  # (the slot may have died in this very frame: its search goes with it)
                 cell_of[s], proj[s] = cell, (F(x), F(y), F(p["idepth_init"]), F(p["var_init"]))
                 cell_key[cell] = (int(F(p["var_init"]).view(np.uint32)), s)
             self.pf_used[cur_pf], self.pf_id[cur_pf], self.pf_T[cur_pf], self.pf_img[cur_pf] = True, int(img_id), T.copy(), cur
             self.pf_added += 1
         self.counts[NEW], self.dropped = n_new, dropped
         em = [s for s in sorted(cell_of) if self.alive[s] and cell_key[cell_of[s]][1] == s]
-        return dict(vtx=np.array([[proj[s][0], proj[s][1]] for s in em], np.float32).reshape(-1, 2),
-                    idepth_mu=np.array([proj[s][2] for s in em], np.float32), idepth_var=np.array([proj[s][3] for s in em], np.float32),
-                    slot=np.array(em, np.int32), status=np.array([self.status[s] for s in em], np.int32))
+        self.image = img.copy()
+        self.emitted = dict(vtx=np.array([[proj[s][0], proj[s][1]] for s in em], np.float32).reshape(-1, 2),
+                            idepth_mu=np.array([proj[s][2] for s in em], np.float32),
+                            idepth_var=np.array([proj[s][3] for s in em], np.float32),
+                            slot=np.array(em, np.int32), status=np.array([self.status[s] for s in em], np.int32))
+        return self.emitted
 
     def _kill(self):
         for s in range(self.F):
@@ -294,6 +457,18 @@ class FrontEndRef:
     def state(self):
         return dict(alive=self.alive.copy(), u=self.u.copy(), v=self.v.copy(), pf=self.pf.copy(), mu=self.mu.copy(),
                     var=self.var.copy(), drop=self.drop.copy(), status=self.status.copy(), kstar=self.kstar.copy())
+
+    def searches(self):
+        return dict(seg=self.seg.copy(), steps=self.steps.copy())
+
+    def debug_image(self, kind):
+        if kind == D.IMG_MATCHES:
+            return D.draw_matches(self.image, self.status, self.kstar, self.seg, self.steps)
+        return D.draw_detections(self.image, self.emitted["vtx"], self.emitted["status"])
+
+    def warp_refused(self):
+        """Of the last frame."""
+        return self.counts.get("warp_refused", 0)
 
 
 # ---------------------------------------------------------------- scenes ----
@@ -358,3 +533,12 @@ def plane_scene(seed, frames=6):
             fv * fu * low[v0 + 1, u0 + 1]
         out.append((np.floor(val + 0.5).astype(np.uint8), T))
     return out
+
+
+# The switches' rule modules (see the top of the file): they import this module, which is complete at this point.
+from tests import fe_debug_ref as D  # noqa: E402
+from tests import fe_gates_ref as G  # noqa: E402
+from tests import fe_gi_ref as GI  # noqa: E402
+from tests import fe_rg_ref as RG  # noqa: E402
+from tests import fe_warp_ref as WR  # noqa: E402
+from tests import fe_zm_ref as Z  # noqa: E402

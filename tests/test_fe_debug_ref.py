@@ -151,7 +151,7 @@ def test_detection_squares_clip_at_the_corners_and_new_lies_over_tracked():
 def ten_frames():
     """frontend_scenes "sideways", ten frames, frame 0 the only pose frame, 256 slots, default parameters: per frame the emitted
     list, the state, the record and both pictures (computed once, read-only)."""
-    ref = D.DebugRef(SC.W, SC.H, SC.K, 256, 4)
+    ref = R.FrontEndRef(SC.W, SC.H, SC.K, 256, 4)
     base = R.FrontEndRef(SC.W, SC.H, SC.K, 256, 4)
     p, out = R.params(), []
     for k, (img, T) in enumerate(SC.scene("sideways", 1, frames=10)):

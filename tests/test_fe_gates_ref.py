@@ -33,7 +33,7 @@ def test_band_arithmetic():
     G.check_band(37, 5)
     with pytest.raises(ValueError):
         G.check_band(8, 5)          # rows 2 ... 5: four rows, a candidate row with its windows needs seven
-    ref = G.GatesRef(48, 8, K_SMALL, 16, 2)
+    ref = R.FrontEndRef(48, 8, K_SMALL, 16, 2)
     ref.set_gates(letterbox=True)
     with pytest.raises(ValueError):
         ref.track(R.params(), np.zeros((8, 48), np.uint8), 0, R.pose(), True)
@@ -55,7 +55,7 @@ def test_letterbox_detection_rows():
     the ungated detector (32 < H - m) in cell row 2."""
     img = _spots([(8, 10, 255), (8, 14, 130), (24, 33, 255), (40, 20, 200)])
     p = R.params()
-    plain, gated = G.GatesRef(48, 36, K_SMALL, 32, 2), G.GatesRef(48, 36, K_SMALL, 32, 2)
+    plain, gated = R.FrontEndRef(48, 36, K_SMALL, 32, 2), R.FrontEndRef(48, 36, K_SMALL, 32, 2)
     gated.set_gates(letterbox=True)
     o0, o1 = plain.track(p, img, 0, R.pose(), True), gated.track(p, img, 0, R.pose(), True)
     at0 = {(int(x), int(y)) for x, y in o0["vtx"]}
@@ -65,11 +65,11 @@ def test_letterbox_detection_rows():
     assert all(12 <= y <= 23 for _, y in at1)
     # the clip of cell row 0 is rows 12...15 exactly: a spot whose gradient sits at rows 11 and 16 is seen by cell row 1 only
     img2 = _spots([(8, 17, 255)])            # gradient at (8, 16), (8, 18), (7, 17), (9, 17)
-    g2 = G.GatesRef(48, 36, K_SMALL, 32, 2)
+    g2 = R.FrontEndRef(48, 36, K_SMALL, 32, 2)
     g2.set_gates(letterbox=True)
     assert {(int(x), int(y)) for x, y in g2.track(p, img2, 0, R.pose(), True)["vtx"]} == {(8, 16)}
     img3 = _spots([(8, 11, 255)])            # gradient at (8, 10), (8, 12), (7, 11), (9, 11): row 12 is the band's first
-    g3 = G.GatesRef(48, 36, K_SMALL, 32, 2)
+    g3 = R.FrontEndRef(48, 36, K_SMALL, 32, 2)
     g3.set_gates(letterbox=True)
     assert {(int(x), int(y)) for x, y in g3.track(p, img3, 0, R.pose(), True)["vtx"]} == {(8, 12)}
 
@@ -84,7 +84,7 @@ def test_letterbox_projection_crossing_the_last_row(ty, refused):
     so the detector plants a new feature there.  At 22.5 it is emitted and the cell stays its own."""
     img = _spots([(8, 24, 255)])  # the band's last row carries the gradient: detection at (8, 23)
     p = R.params()
-    ref = G.GatesRef(48, 36, K_SMALL, 32, 2)
+    ref = R.FrontEndRef(48, 36, K_SMALL, 32, 2)
     ref.set_gates(letterbox=True)
     o = ref.track(p, img, 0, R.pose(), True)
     assert [(int(x), int(y)) for x, y in o["vtx"]] == [(8, 23)]
@@ -99,7 +99,7 @@ def test_letterbox_projection_crossing_the_last_row(ty, refused):
         assert ref.refused == 0 and ref.drop[0] == 0
         assert list(o["slot"]) == [0] and o["status"][0] == R.NO_PARALLAX and ref.counts[R.NEW] == 0
     # the same frames without the letterbox: emitted either way
-    plain = G.GatesRef(48, 36, K_SMALL, 32, 2)
+    plain = R.FrontEndRef(48, 36, K_SMALL, 32, 2)
     plain.track(p, img, 0, R.pose(), True)
     assert (plain.u[0], plain.v[0]) == (8, 23)
     o = plain.track(p, img, 1, R.pose((0.0, ty, 0.0)), False)
@@ -110,7 +110,7 @@ def test_letterbox_first_row_and_death():
     """The band's first row, and max_dropouts refusals in a row kill the feature."""
     img = _spots([(8, 11, 255)])  # detection at (8, 12)
     p = R.params(max_dropouts=1)
-    ref = G.GatesRef(48, 36, K_SMALL, 32, 2)
+    ref = R.FrontEndRef(48, 36, K_SMALL, 32, 2)
     ref.set_gates(letterbox=True)
     ref.track(p, img, 0, R.pose(), True)
     assert (ref.u[0], ref.v[0]) == (8, 12)
@@ -125,7 +125,7 @@ def test_letterbox_first_row_and_death():
 def test_height_holder_leaves_the_emission_to_the_other_feature():
     c, p, plain, out_plain, (cell, win, lose), h = G.colliding_runs()
     assert win in out_plain["slot"] and lose not in out_plain["slot"]
-    ref = G.GatesRef(FC.W, FC.H, c.K, FC.SLOTS, FC.RING)
+    ref = R.FrontEndRef(FC.W, FC.H, c.K, FC.SLOTS, FC.RING)
     for call in c.calls[:2]:
         ref.track(p, call[1], call[4], call[2], call[3])
     ref.set_gates(min_height=h[lose], max_height=h[lose], up=(0, 1, 0))  # min_height == max_height: a band of one value
@@ -162,7 +162,7 @@ def test_nan_height_is_held():
     img = _spots([(8, 19, 255)])  # detection at (8, 18); cy = 18
     for init, held in ((0.0, True), (0.5, False)):
         p = R.params(idepth_init=init)
-        ref = G.GatesRef(48, 36, K_SMALL, 32, 2)
+        ref = R.FrontEndRef(48, 36, K_SMALL, 32, 2)
         ref.set_gates(min_height=-G.BIG, max_height=G.BIG, up=(0, 1, 0))
         ref.track(p, img, 0, R.pose(), True)
         assert (ref.u[0], ref.v[0]) == (8, 18)
@@ -180,7 +180,7 @@ def test_no_gate_is_the_base_class():
     fr = SC.scene("diagonal_roll", 1)
     p = R.params()
     base = R.FrontEndRef(SC.W, SC.H, SC.K, 256, 4)
-    a, b = G.GatesRef(SC.W, SC.H, SC.K, 256, 4), G.GatesRef(SC.W, SC.H, SC.K, 256, 4)
+    a, b = R.FrontEndRef(SC.W, SC.H, SC.K, 256, 4), R.FrontEndRef(SC.W, SC.H, SC.K, 256, 4)
     b.set_gates(letterbox=True, max_height=0.0)
     b.set_gates()
     for k, (img, T) in enumerate(fr):
@@ -238,7 +238,7 @@ def test_height_band_against_ground_truth(name):
     lo, hi = G.BANDS[name]
     frames = SC.scene(name, 1)
     p = R.params()
-    ref = G.GatesRef(SC.W, SC.H, SC.K, 256, 4)
+    ref = R.FrontEndRef(SC.W, SC.H, SC.K, 256, 4)
     ref.set_gates(min_height=lo, max_height=hi, up=(0, 1, 0))
     lo, hi = -np.inf if lo is None else lo, np.inf if hi is None else hi
     n_conv = n_margin = n_out_held = n_in_emitted = 0

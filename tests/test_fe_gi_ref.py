@@ -44,7 +44,7 @@ def make_ref(cur_win, ref_win):
     cur, ref = np.zeros((n, n), np.int64), np.zeros((n, n), np.int64)
     cur[1:win + 2, 1:win + 2] = cur_win
     ref[1:win + 1, 1:win + 1] = ref_win
-    return GI.GiRef(n, n, np.array([10, 0, 6, 0, 10, 6, 0, 0, 1], np.float32), 4, 1), cur, ref, win
+    return R.FrontEndRef(n, n, np.array([10, 0, 6, 0, 10, 6, 0, 0, 1], np.float32), 4, 1), cur, ref, win
 
 
 def window_cost(cur_win, ref_win, mode="gi", qx=0, qy=0):
@@ -167,7 +167,7 @@ def test_the_double_path_equals_exact_arithmetic_on_random_windows():
     assert seen >= 100
 
 
-class Injected(GI.GiRef):
+class Injected(R.FrontEndRef):
     """One live feature at (24, 18) of pose frame 0 whose search has exactly six samples; the costs are hand-written.  The pose
     frame is a one-pixel chessboard of 0 / 255 (ZR = 600 * 65 280^2 at win 7: above every injected cost) or flat."""
     TX = 0.02  # L = 140 * 0.02 * (1.5 - 0.01) = 4.17: S = 5
@@ -262,7 +262,7 @@ def test_gain_moves_the_zssd_minimum_to_the_neighbour_and_not_this_rules():
 # ---- 2. exact invariance ----
 
 def run_frames(frames, win, mode, poseframes=GS.POSEFRAMES):
-    ref = GI.GiDebugRef(ZS.W, ZS.H, ZS.K, 256, 4)
+    ref = R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4)
     ref.set_cost(mode == "zssd")
     ref.set_gain_invariant(mode == "gi")
     p = R.params(win_size=win)
@@ -296,7 +296,7 @@ def test_power_of_two_gain_and_offsets_change_nothing_under_this_rule_and_someth
 def test_switch_off_is_the_base_class():
     p = R.params(win_size=7)
     for zm in (False, True):
-        a, b = GI.GiRef(ZS.W, ZS.H, ZS.K, 256, 4), Z.ZmRef(ZS.W, ZS.H, ZS.K, 256, 4)
+        a, b = R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4), R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4)
         a.set_cost(zm)
         b.set_cost(zm)
         a.set_gain_invariant(True)

@@ -90,7 +90,7 @@ def test_ring_leaving_the_image():
     assert RG.structure_tensor(img, 3, 3, 5) is not None and RG.structure_tensor(img, 2, 3, 5) is None and RG.structure_tensor(img, 4, 3, 7) is None
     # in the tracker: detected at win 3 on the right margin (W - 3, 18), tracked at win 5 -> OUTSIDE, one dropout, no search
     img, second, T0, T1 = margin_scene()
-    fe = RG.RgRef(MW, MH, MK, 32, 2)
+    fe = R.FrontEndRef(MW, MH, MK, 32, 2)
     fe.set_ref_grad(G0)
     fe.track(R.params(win_size=3), img, 0, T0, True)
     s, = np.flatnonzero((fe.alive > 0) & (fe.u == MW - 3) & (fe.v == 18))
@@ -108,14 +108,14 @@ def test_a_nan_refuses():
         assert not RG.passes(E, 2, 2, S, 3, 1.0), E
     assert not RG.passes((3, 2, 1), 2, 2, S, 3, np.nan)
     with pytest.raises(ValueError):
-        RG.RgRef(48, 36, SC.K, 8, 1).set_ref_grad(float("nan"))
+        R.FrontEndRef(48, 36, SC.K, 8, 1).set_ref_grad(float("nan"))
     with pytest.raises(ValueError):
-        RG.RgRef(48, 36, SC.K, 8, 1).set_ref_grad(-1.0)
+        R.FrontEndRef(48, 36, SC.K, 8, 1).set_ref_grad(-1.0)
 
 
 def test_gate_off_is_the_base_class():
     p = R.params(win_size=7)
-    a, b = RG.RgRef(ZS.W, ZS.H, ZS.K, 256, 4), R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4)
+    a, b = R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4), R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4)
     a.set_ref_grad(G0)
     a.set_ref_grad(0.0)
     for k, (img, T) in enumerate(RG.half_striped("sideways")[:3]):
@@ -125,7 +125,7 @@ def test_gate_off_is_the_base_class():
 
 def test_a_refused_feature_is_a_failure_like_ambiguous():
     """Prior and k* untouched, no search, one dropout a frame, death past max_dropouts, counted under its own status."""
-    fe, outs, dec = RG.run(RG.half_striped("sideways")[:4], min_grad=G0, win_size=7, max_dropouts=3, ref=RG.RgDebugRef)
+    fe, outs, dec = RG.run(RG.half_striped("sideways")[:4], min_grad=G0, win_size=7, max_dropouts=3)
     refused = fe.status == RG.REF_GRAD
     assert refused.sum() >= 25 and (fe.drop[refused] == 3).all() and (fe.kstar[refused] == -1).all()
     assert (fe.mu[refused] == F(0.5)).all() and (fe.var[refused] == F(0.25)).all()
@@ -168,7 +168,7 @@ ROUNDINGS, DIR_ROUNDINGS, EPS = 6, 3, 2.0 ** -24
 
 @pytest.mark.parametrize("name", SC.NAMES)
 def test_decision_against_float64_geometry(name):
-    fe = RG.RgRef(SC.W, SC.H, SC.K, 256, 4)
+    fe = R.FrontEndRef(SC.W, SC.H, SC.K, 256, 4)
     fe.set_ref_grad(G0)
     p = R.params()
     n = inside = close = 0

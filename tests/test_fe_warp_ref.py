@@ -75,7 +75,7 @@ def small_images(seed=3):
 
 
 def make(cost):
-    fe = WR.WarpRef(SW, SH, np.array([20, 0, 11.5, 0, 20, 11.5, 0, 0, 1], np.float32), 8, 2)
+    fe = R.FrontEndRef(SW, SH, np.array([20, 0, 11.5, 0, 20, 11.5, 0, 0, 1], np.float32), 8, 2)
     fe.set_cost(cost == "zssd")
     fe.set_gain_invariant(cost == "gi")
     return fe
@@ -195,7 +195,7 @@ def test_the_edges_of_the_two_tests():
 @pytest.mark.parametrize("kind", ["closer", "grazing"])
 def test_refused_features(kind):
     img, T0 = WS.scene("roll30")[0]
-    fe = WR.WarpDebugRef(WS.W, WS.H, WS.K, 256, 4)
+    fe = R.FrontEndRef(WS.W, WS.H, WS.K, 256, 4)
     fe.set_warp()
     p = R.params(**WS.REFUSAL_PRIOR)
     fe.track(p, img, 0, T0, True)
@@ -215,7 +215,7 @@ def test_refused_features(kind):
         assert fe.mu[s].view(np.uint32) == before["mu"][s].view(np.uint32) and fe.var[s].view(np.uint32) == before["var"][s].view(np.uint32)
         assert fe.steps[s] == 0 and (fe.seg[s] == 0).all()
     # with the switch off the same frame searches every one of them
-    off = WR.WarpDebugRef(WS.W, WS.H, WS.K, 256, 4)
+    off = R.FrontEndRef(WS.W, WS.H, WS.K, 256, 4)
     off.track(p, img, 0, T0, True)
     off.track(p, img, 1, WS.refusal(kind), False)
     assert all(off.steps[m[0]] > 0 for m in refused) and off.warp_refused() == 0
@@ -223,7 +223,7 @@ def test_refused_features(kind):
 
 def test_refused_features_die_after_max_dropouts():
     img, T0 = WS.scene("roll30")[0]
-    fe = WR.WarpDebugRef(WS.W, WS.H, WS.K, 256, 4)
+    fe = R.FrontEndRef(WS.W, WS.H, WS.K, 256, 4)
     fe.set_warp()
     p = R.params(max_dropouts=1, **WS.REFUSAL_PRIOR)
     fe.track(p, img, 0, T0, True)
@@ -248,7 +248,7 @@ def test_j_against_float64_central_differences(name):
     """|Jq / 256 - J| <= 1 / 256 + band per entry, J the central difference of the exact projection at xi_J in float64.  The band is
     counted, not measured: fe_warp_ref.Err carries a first-order error bound through the operations of jacobian32, one rounding of
     2^-24 each, A and c rounded once (it comes to below 1e-6; rounding to the nearest 1/256 itself takes half of the 1/256)."""
-    fe = WR.WarpRef(WS.W, WS.H, WS.K, 256, 4)
+    fe = R.FrontEndRef(WS.W, WS.H, WS.K, 256, 4)
     fe.set_warp()
     p = R.params()
     n, worst, widest = 0, 0.0, 0.0
@@ -274,7 +274,7 @@ def test_pure_translation_changes_no_bit(cost):
     frames = WS.translation()
     runs = []
     for warp in (False, True):
-        fe = WR.WarpDebugRef(WS.W, WS.H, WS.K, 256, 4)
+        fe = R.FrontEndRef(WS.W, WS.H, WS.K, 256, 4)
         fe.set_warp(warp)
         fe.set_cost(cost == "zssd")
         fe.set_gain_invariant(cost == "gi")

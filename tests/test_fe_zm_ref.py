@@ -41,7 +41,7 @@ def window_cost(cur_win, ref_win, zero_mean, qx=0, qy=0):
     cur, ref = np.zeros((n, n), np.int64), np.zeros((n, n), np.int64)
     cur[1:win + 2, 1:win + 2] = cur_win
     ref[1:win + 1, 1:win + 1] = ref_win
-    z = Z.ZmRef(n, n, np.array([10, 0, 6, 0, 10, 6, 0, 0, 1], np.float32), 4, 1)
+    z = R.FrontEndRef(n, n, np.array([10, 0, 6, 0, 10, 6, 0, 0, 1], np.float32), 4, 1)
     z.set_cost(zero_mean)
     return z._cost(cur, ref, 1 + r, 1 + r, F(1 + r) + F(qx) / F(16), F(1 + r) + F(qy) / F(16), win)
 
@@ -100,7 +100,7 @@ def test_saturation_of_the_threshold():
     assert Z.bad_threshold(3.0e38, 9, Z.COST_ZSSD) == top
 
 
-class Injected(Z.ZmRef):
+class Injected(R.FrontEndRef):
     """One live feature at (24, 18) of pose frame 0 whose search has exactly six samples; the costs are hand-written."""
     TX = 0.02  # L = 140 * 0.02 * (1.5 - 0.01) = 4.17: S = 5
 
@@ -171,7 +171,7 @@ def test_offset_moves_the_ssd_minimum_to_the_neighbour_and_not_the_zssd_minimum(
 # ---- 2. exact invariance ----
 
 def run_scene(name, win, zero_mean, offsets=None, poseframes=(0, 4)):
-    ref = Z.ZmDebugRef(ZS.W, ZS.H, ZS.K, 256, 4)
+    ref = R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4)
     ref.set_cost(zero_mean)
     p = R.params(win_size=win)
     rec, out = [], None
@@ -211,7 +211,7 @@ def test_offsets_change_nothing_under_zssd_and_something_under_ssd(name, win):
 
 def test_ssd_mode_is_the_base_class():
     p = R.params()
-    a, b = Z.ZmRef(ZS.W, ZS.H, ZS.K, 256, 4), R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4)
+    a, b = R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4), R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4)
     a.set_cost(True)
     a.set_cost(False)
     for k, (img, T) in enumerate(ZS.scene("sideways", 1)[:3]):

@@ -10,76 +10,9 @@ from tests import fe_debug_ref as D
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
 from tests import ingest_ref as IR
+from tests.fe_pair import pair  # noqa: F401  (pair: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-def same_picture(tag, got, want):
-    assert got.shape == want.shape and got.dtype == np.uint8, tag
-    bad = np.argwhere((got != want).any(axis=2))
-    assert len(bad) == 0, "%s: %d pixels differ, first (y, x) %s: gpu %s restatement %s" % (
-        tag, len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
-
-
-class Pair:
-    """One GPU handle and one restatement fed the same calls; the record and both pictures are compared after every frame."""
-
-    def __init__(self, W, H, max_features=256, max_poseframes=4, K=R.SCENE_K, pitch=None, out_pitch=None, **kw):
-        from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
-        self.gpu = GpuFrontEnd(W, H, K, max_features, max_poseframes)
-        self.ref = D.DebugRef(W, H, K, max_features, max_poseframes)
-        self.pr, self.pg = R.params(**kw), default_frontend_params(**kw)
-        self.W, self.H, self.pitch, self.out_pitch, self.frame = W, H, pitch, out_pitch, 0
-
-    def close(self):
-        self.gpu.close()
-
-    def track(self, img, T, is_pf, img_id=None, raw=None):
-        """`raw`: the GPU takes this raw image through track_raw, the restatement the rectified `img`."""
-        img_id = self.frame if img_id is None else img_id
-        gimg = img
-        if self.pitch:  # rows `pitch` bytes apart, the image starting at an odd address
-            buf = np.full(img.shape[0] * self.pitch + 1, 0xAB, np.uint8)
-            gimg = np.lib.stride_tricks.as_strided(buf[1:], img.shape, (self.pitch, 1))
-            gimg[...] = img
-        want = self.ref.track(self.pr, img, img_id, T, is_pf)
-        got = self.gpu.track_raw(self.pg, raw, img_id, T, is_pf) if raw is not None else self.gpu.track(self.pg, gimg, img_id, T, is_pf)
-        assert np.array_equal(got["slot"], want["slot"]) and np.array_equal(got["status"], want["status"])
-        self.check("frame %d" % self.frame)
-        self.frame += 1
-        return want
-
-    def check(self, tag):
-        st = self.gpu.state()
-        assert np.array_equal(st["status"], self.ref.status) and np.array_equal(st["kstar"], self.ref.kstar), tag
-        got, want = self.gpu.searches(), self.ref.searches()
-        assert np.array_equal(got["steps"], want["steps"]), "%s: steps differ at %s" % (tag, np.flatnonzero(got["steps"] != want["steps"])[:5])
-        bad = np.flatnonzero((got["seg"].view(np.uint32) != want["seg"].view(np.uint32)).any(axis=1))
-        assert len(bad) == 0, "%s: seg differs at %s: gpu %s restatement %s" % (tag, bad[:5], got["seg"][bad[:5]], want["seg"][bad[:5]])
-        pics = {}
-        for kind, name in ((D.IMG_MATCHES, "matches"), (D.IMG_DETECTIONS, "detections")):
-            if self.out_pitch:  # the bytes between the rows stay what they were
-                buf = np.full(self.H * self.out_pitch, 0xAB, np.uint8)
-                pic = self.gpu.debug_image(kind, pitch=self.out_pitch, out=buf)
-                rows = buf.reshape(self.H, self.out_pitch)
-                assert (rows[:, 3 * self.W:] == 0xAB).all(), "%s %s: padding bytes written" % (tag, name)
-            else:
-                pic = self.gpu.debug_image(kind)
-            same_picture("%s %s" % (tag, name), pic, self.ref.debug_image(kind))
-            pics[name] = np.array(pic)
-        return pics
-
-
-@pytest.fixture
-def pair(gpu):
-    made = []
-
-    def make(*a, **kw):
-        made.append(Pair(*a, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
 
 
 def count(im, colour):

@@ -12,74 +12,10 @@ from tests import fe_gates_ref as G
 from tests import frontend_corpus as FC
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
+from tests.fe_pair import pair  # noqa: F401  (pair: the fixture)
 
 pytestmark = pytest.mark.gpu
 K_4837 = np.array([140, 0, 23.5, 0, 140, 18, 0, 0, 1], np.float32)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def compare(tag, got, want):
-    for k in want:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.shape == w.shape, "%s: %s has shape %s, restatement %s" % (tag, k, g.shape, w.shape)
-        bad = np.flatnonzero((bits(g) != bits(w)).reshape(len(w), -1).any(axis=1)) if len(w) else []
-        assert len(bad) == 0, "%s: %s differs at %s: gpu %s restatement %s" % (tag, k, bad[:5], g[bad[:5]], w[bad[:5]])
-
-
-class Pair:
-    """One GPU handle and one restatement fed the same calls."""
-
-    def __init__(self, W, H, max_features=256, max_poseframes=4, K=R.SCENE_K, ref=None, **kw):
-        from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
-        self.gpu = GpuFrontEnd(W, H, K, max_features, max_poseframes)
-        self.ref = (ref or G.GatesDebugRef)(W, H, K, max_features, max_poseframes)
-        self.pr, self.pg = R.params(**kw), default_frontend_params(**kw)
-        self.frame = 0
-        self.total = dict(held=0, refused=0, died=0, new=0, emitted=0)
-
-    def close(self):
-        self.gpu.close()
-
-    def set_gates(self, **kw):
-        self.gpu.set_gates(**kw)
-        self.ref.set_gates(**kw)
-
-    def track(self, img, T, is_pf, img_id=None):
-        img_id = self.frame if img_id is None else img_id
-        want = self.ref.track(self.pr, img, img_id, T, is_pf)
-        got = self.gpu.track(self.pg, img, img_id, T, is_pf)
-        tag = "frame %d" % self.frame
-        compare(tag, got, want)
-        compare(tag + " state", self.gpu.state(), self.ref.state())
-        if hasattr(self.ref, "searches"):
-            compare(tag + " searches", self.gpu.searches(), self.ref.searches())
-        for st, key in enumerate(("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died")):
-            assert self.gpu.info(key) == self.ref.counts.get(st, 0), (tag, key)
-        assert self.gpu.info("emitted") == len(want["slot"]) and self.gpu.info("detections_dropped") == self.ref.dropped
-        assert self.gpu.info("live") == int(self.ref.alive.sum())
-        held, refused = getattr(self.ref, "held", 0), getattr(self.ref, "refused", 0)
-        assert self.gpu.info("held_height") == held and self.gpu.info("refused_letterbox") == refused, tag
-        for k, v in (("held", held), ("refused", refused), ("died", self.ref.counts.get(R.DIED, 0)), ("new", self.ref.counts.get(R.NEW, 0)),
-                     ("emitted", len(want["slot"]))):
-            self.total[k] += v
-        self.frame += 1
-        return want
-
-
-@pytest.fixture
-def pair(gpu):
-    made = []
-
-    def make(*a, **kw):
-        made.append(Pair(*a, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
 
 
 def test_letterbox_48x37(pair):
@@ -175,9 +111,9 @@ def test_both_gates_then_cleared_then_set_again(pair):
 
 @pytest.mark.parametrize("how", ["never_set", "switches_off", "set_and_cleared"])
 def test_no_gate_changes_nothing(pair, how):
-    """The no-behaviour-change proof: against frontend_ref.FrontEndRef itself (which knows no gates) on "diagonal_roll"."""
+    """The no-behaviour-change proof: against frontend_ref.FrontEndRef with every switch off on "diagonal_roll"."""
     from flame_ros_amd import frontend as FE
-    p = pair(SC.W, SC.H, K=SC.K, ref=R.FrontEndRef)
+    p = pair(SC.W, SC.H, K=SC.K)
     if how == "switches_off":
         g = FE.Gates(0, 0, 0.25, -0.25, (C.c_float * 3)(0.0, 0.0, 0.0))  # (the other fields are not read)
         assert p.gpu._lib.flame_hip_frontend_set_gates(p.gpu._h, C.byref(g)) == 0

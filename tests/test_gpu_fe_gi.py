@@ -9,103 +9,15 @@ import pytest
 from tests import fe_debug_ref as D
 from tests import fe_gi_ref as GI
 from tests import fe_gi_scenes as GS
+from tests import fe_zm_ref as Z
 from tests import fe_zm_scenes as ZS
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
+from tests.fe_pair import compare, pair  # noqa: F401  (pair: the fixture)
 
 pytestmark = pytest.mark.gpu
 K_4836 = np.array([140, 0, 23.5, 0, 140, 17.5, 0, 0, 1], np.float32)
 STATUS_KEYS = ("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died")
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def compare(tag, got, want):
-    for k in want:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.shape == w.shape, "%s: %s has shape %s, restatement %s" % (tag, k, g.shape, w.shape)
-        bad = np.flatnonzero((bits(g) != bits(w)).reshape(len(w), -1).any(axis=1)) if len(w) else []
-        assert len(bad) == 0, "%s: %s differs at %s: gpu %s restatement %s" % (tag, k, bad[:5], g[bad[:5]], w[bad[:5]])
-
-
-class Pair:
-    """One GPU handle and one restatement fed the same calls."""
-
-    def __init__(self, W, H, max_features=256, max_poseframes=4, K=R.SCENE_K, ref=None, **kw):
-        from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
-        self.gpu = GpuFrontEnd(W, H, K, max_features, max_poseframes)
-        self.ref = (ref or GI.GiGatesDebugRef)(W, H, K, max_features, max_poseframes)
-        self.pr, self.pg = R.params(**kw), default_frontend_params(**kw)
-        self.frame = 0
-        self.total = dict(held=0, refused=0, emitted=0, ref_grad=0)
-        self.total.update({k: 0 for k in STATUS_KEYS})
-        self.record = []  # per frame: what the GPU gave (features, state, searches)
-
-    def close(self):
-        self.gpu.close()
-
-    def set_gain_invariant(self, on=True):
-        self.gpu.set_gain_invariant(on)
-        self.ref.set_gain_invariant(on)
-        assert self.gpu.info("gain_invariant") == int(self.ref.gain_invariant) == int(on)
-        assert self.gpu.info("cost_mode") == self.ref.cost_mode  # (untouched)
-
-    def set_cost(self, zero_mean=True):
-        self.gpu.set_cost(zero_mean)
-        self.ref.set_cost(zero_mean)
-        assert self.gpu.info("cost_mode") == self.ref.cost_mode
-
-    def set_gates(self, **kw):
-        self.gpu.set_gates(**kw)
-        self.ref.set_gates(**kw)
-
-    def set_ref_grad(self, g):
-        self.gpu.set_ref_grad(g)
-        self.ref.set_ref_grad(g)
-
-    def track(self, img, T, is_pf, img_id=None):
-        img_id = self.frame if img_id is None else img_id
-        want = self.ref.track(self.pr, img, img_id, T, is_pf)
-        got = self.gpu.track(self.pg, img, img_id, T, is_pf)
-        tag = "frame %d" % self.frame
-        compare(tag, got, want)
-        state = self.gpu.state()
-        compare(tag + " state", state, self.ref.state())
-        searches = None
-        if hasattr(self.ref, "searches"):
-            searches = self.gpu.searches()
-            compare(tag + " searches", searches, self.ref.searches())
-        for st, key in enumerate(STATUS_KEYS):
-            assert self.gpu.info(key) == self.ref.counts.get(st, 0), (tag, key)
-            self.total[key] += self.ref.counts.get(st, 0)
-        rg = self.ref.counts.get(7, 0)  # REF_GRAD
-        assert self.gpu.info("fail_ref_grad") == rg, tag
-        self.total["ref_grad"] += rg
-        assert self.gpu.info("emitted") == len(want["slot"]) and self.gpu.info("detections_dropped") == self.ref.dropped
-        assert self.gpu.info("live") == int(self.ref.alive.sum())
-        held, refused = getattr(self.ref, "held", 0), getattr(self.ref, "refused", 0)
-        assert self.gpu.info("held_height") == held and self.gpu.info("refused_letterbox") == refused, tag
-        self.total["held"] += held
-        self.total["refused"] += refused
-        self.total["emitted"] += len(want["slot"])
-        self.record.append((got, state, searches))
-        self.frame += 1
-        return want
-
-
-@pytest.fixture
-def pair(gpu):
-    made = []
-
-    def make(*a, **kw):
-        made.append(Pair(*a, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
 
 
 def spy_costs(p):
@@ -218,7 +130,7 @@ def test_identical_and_flat_current_windows(pair):
     before = p.total["bad_match"]
     p.track(np.full((H, W), 77, np.uint8), R.pose((0.03, 0.0, 0.0)), False)
     costs = [c for c in seen if c is not None]
-    assert costs and min(costs) > GI.Z.bad_threshold(100.0, 5, GI.Z.COST_ZSSD)
+    assert costs and min(costs) > Z.bad_threshold(100.0, 5, Z.COST_ZSSD)
     assert p.total["bad_match"] - before >= 4
 
 
@@ -279,7 +191,7 @@ def test_switched_on_off_and_on_in_mid_sequence(pair, zero_mean):
 
 
 def test_with_both_gates_and_the_gradient_gate(pair):
-    p = pair(ZS.W, ZS.H, K=ZS.K, win_size=7, ref=GI.RgGiGatesDebugRef)
+    p = pair(ZS.W, ZS.H, K=ZS.K, win_size=7)
     p.set_gain_invariant()
     p.set_gates(letterbox=True, max_height=0.05, up=(0, 1, 0))
     p.set_ref_grad(12.0)
@@ -311,8 +223,8 @@ def test_matches_image_of_a_gain_invariant_frame(pair):
 
 @pytest.mark.parametrize("how", ["never_set", "set_and_cleared"])
 def test_switch_off_changes_nothing(pair, how):
-    """The no-behaviour-change proof: against frontend_ref.FrontEndRef itself (which knows no cost at all) on "diagonal_roll"."""
-    p = pair(SC.W, SC.H, K=SC.K, ref=R.FrontEndRef)
+    """The no-behaviour-change proof: against frontend_ref.FrontEndRef with every switch off on "diagonal_roll"."""
+    p = pair(SC.W, SC.H, K=SC.K)
     if how == "set_and_cleared":
         p.gpu.set_gain_invariant()
         assert p.gpu.info("gain_invariant") == 1

@@ -10,6 +10,7 @@ from tests import fe_rg_ref as RG
 from tests import fe_zm_scenes as ZS
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
+from tests.fe_pair import pair  # noqa: F401  (pair: the fixture)
 
 pytestmark = pytest.mark.gpu
 K_4836 = np.array([140, 0, 23.5, 0, 140, 17.5, 0, 0, 1], np.float32)
@@ -17,91 +18,11 @@ STATUS_KEYS = ("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", 
 G0 = 5.0
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def compare(tag, got, want):
-    for k in want:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.shape == w.shape, "%s: %s has shape %s, restatement %s" % (tag, k, g.shape, w.shape)
-        bad = np.flatnonzero((bits(g) != bits(w)).reshape(len(w), -1).any(axis=1)) if len(w) else []
-        assert len(bad) == 0, "%s: %s differs at %s: gpu %s restatement %s" % (tag, k, bad[:5], g[bad[:5]], w[bad[:5]])
-
-
-class Pair:
-    """One GPU handle and one restatement fed the same calls."""
-
-    def __init__(self, W, H, max_features=256, max_poseframes=4, K=ZS.K, ref=None, **kw):
-        from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
-        self.gpu = GpuFrontEnd(W, H, K, max_features, max_poseframes)
-        self.ref = (ref or RG.RgZmGatesDebugRef)(W, H, K, max_features, max_poseframes)
-        self.pr, self.pg = R.params(**kw), default_frontend_params(**kw)
-        self.frame = 0
-        self.total = dict(held=0, refused=0, emitted=0, ref_grad=0)
-        self.total.update({k: 0 for k in STATUS_KEYS})
-        self.ref_grad = []  # REF_GRAD count per frame
-
-    def close(self):
-        self.gpu.close()
-
-    def set_ref_grad(self, g):
-        self.gpu.set_ref_grad(g)
-        self.ref.set_ref_grad(g)
-        assert self.gpu.info("ref_grad") == int(g > 0)
-
-    def set_cost(self, zero_mean=True):
-        self.gpu.set_cost(zero_mean)
-        self.ref.set_cost(zero_mean)
-
-    def set_gates(self, **kw):
-        self.gpu.set_gates(**kw)
-        self.ref.set_gates(**kw)
-
-    def track(self, img, T, is_pf):
-        want = self.ref.track(self.pr, img, self.frame, T, is_pf)
-        got = self.gpu.track(self.pg, img, self.frame, T, is_pf)
-        tag = "frame %d" % self.frame
-        compare(tag, got, want)
-        compare(tag + " state", self.gpu.state(), self.ref.state())
-        if hasattr(self.ref, "searches"):
-            compare(tag + " searches", self.gpu.searches(), self.ref.searches())
-        for st, key in enumerate(STATUS_KEYS):
-            assert self.gpu.info(key) == self.ref.counts.get(st, 0), (tag, key)
-            self.total[key] += self.ref.counts.get(st, 0)
-        n_rg = self.ref.counts.get(RG.REF_GRAD, 0)
-        assert self.gpu.info("fail_ref_grad") == n_rg, tag
-        assert self.gpu.info("emitted") == len(want["slot"]) and self.gpu.info("detections_dropped") == self.ref.dropped
-        assert self.gpu.info("live") == int(self.ref.alive.sum())
-        held, refused = getattr(self.ref, "held", 0), getattr(self.ref, "refused", 0)
-        assert self.gpu.info("held_height") == held and self.gpu.info("refused_letterbox") == refused, tag
-        self.total["held"] += held
-        self.total["refused"] += refused
-        self.total["emitted"] += len(want["slot"])
-        self.total["ref_grad"] += n_rg
-        self.ref_grad.append(n_rg)
-        self.frame += 1
-        return want
-
-
-@pytest.fixture
-def pair(gpu):
-    made = []
-
-    def make(*a, **kw):
-        made.append(Pair(*a, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
-
-
 @pytest.mark.parametrize("name", ["sideways", "vertical"])
 def test_half_striped_scenes(pair, name):
     """The ground-truth test's scenes: the striped half is refused, the isotropic half is tracked; a refused feature keeps its
     prior, takes its dropouts and dies with the sixth."""
-    p = pair(ZS.W, ZS.H, win_size=7)
+    p = pair(ZS.W, ZS.H, K=ZS.K, win_size=7)
     p.set_ref_grad(G0)
     for k, (img, T) in enumerate(RG.half_striped(name)):
         p.track(img, T, k == 0)
@@ -109,7 +30,7 @@ def test_half_striped_scenes(pair, name):
         assert (p.ref.kstar[refused] == -1).all() and (p.ref.steps[refused] == 0).all() and (p.ref.drop[refused] == k).all()
         assert (p.ref.mu[refused] == np.float32(0.5)).all() and (p.ref.var[refused] == np.float32(0.25)).all()
     assert p.ref_grad[0] == 0 and min(p.ref_grad[1:]) >= 25 and p.total["ok"] >= 150, (p.ref_grad, p.total)
-    q = pair(ZS.W, ZS.H, win_size=7, max_dropouts=3)  # ... and death: the refused features die in the fourth tracking frame
+    q = pair(ZS.W, ZS.H, K=ZS.K, win_size=7, max_dropouts=3)  # ... and death: the refused features die in the fourth tracking frame
     q.set_ref_grad(G0)
     for k, (img, T) in enumerate(RG.half_striped(name)[:5]):
         before = q.total["died"]
@@ -134,7 +55,7 @@ def test_general_motion(pair, name):
 @pytest.mark.parametrize("along", ["x", "y"])
 def test_direction_comes_from_the_reference_image(pair, along):
     """Rolled by pi / 2: the line runs along x in the reference image and along y in the current one."""
-    p = pair(ZS.W, ZS.H, win_size=7)
+    p = pair(ZS.W, ZS.H, K=ZS.K, win_size=7)
     p.set_ref_grad(G0)
     for k, (img, T) in enumerate(RG.rolled(along)):
         p.track(img, T, k == 0)
@@ -180,7 +101,7 @@ def test_ring_leaves_the_image_when_the_window_grew(pair):
 
 def test_gate_switched_in_mid_sequence(pair):
     """Off -> on -> off: the state holds no gate, every frame is the current setting's on the state it finds."""
-    p = pair(ZS.W, ZS.H, win_size=7)
+    p = pair(ZS.W, ZS.H, K=ZS.K, win_size=7)
     for k, (img, T) in enumerate(RG.half_striped("sideways")):
         if k in (2, 4):
             p.set_ref_grad(G0 if k == 2 else 0.0)
@@ -190,7 +111,7 @@ def test_gate_switched_in_mid_sequence(pair):
 
 
 def test_with_zssd(pair):
-    p = pair(ZS.W, ZS.H, win_size=7)
+    p = pair(ZS.W, ZS.H, K=ZS.K, win_size=7)
     p.set_cost()
     p.set_ref_grad(G0)
     assert p.gpu.info("cost_mode") == 1 and p.gpu.info("ref_grad") == 1
@@ -201,7 +122,7 @@ def test_with_zssd(pair):
 
 def test_with_both_gates(pair):
     """The letterbox refuses projections of REF_GRAD features too: still one dropout per frame."""
-    p = pair(ZS.W, ZS.H, win_size=7)
+    p = pair(ZS.W, ZS.H, K=ZS.K, win_size=7)
     p.set_gates(letterbox=True, max_height=0.05, up=(0, 1, 0))
     p.set_ref_grad(G0)
     assert p.gpu.info("gates") == 3
@@ -212,7 +133,7 @@ def test_with_both_gates(pair):
 
 
 def test_with_zssd_and_both_gates(pair):
-    p = pair(ZS.W, ZS.H, win_size=7)
+    p = pair(ZS.W, ZS.H, K=ZS.K, win_size=7)
     p.set_cost()
     p.set_gates(letterbox=True, max_height=0.05, up=(0, 1, 0))
     p.set_ref_grad(G0)
@@ -222,7 +143,7 @@ def test_with_zssd_and_both_gates(pair):
 
 
 def test_matches_image_of_a_frame_with_refused_slots(pair):
-    p = pair(ZS.W, ZS.H, win_size=7)
+    p = pair(ZS.W, ZS.H, K=ZS.K, win_size=7)
     p.set_ref_grad(G0)
     frames = RG.half_striped("sideways")
     for k, (img, T) in enumerate(frames[:3]):
@@ -234,7 +155,7 @@ def test_matches_image_of_a_frame_with_refused_slots(pair):
     colour = lambda im, c: (im == np.array(c, np.uint8)).all(axis=2)  # noqa: E731
     assert colour(got, D.YELLOW).sum() >= 20
     # ... and the refused slots draw nothing: the ungated tracker's picture has searches in the striped half, this one has none
-    q = pair(ZS.W, ZS.H, win_size=7)
+    q = pair(ZS.W, ZS.H, K=ZS.K, win_size=7)
     for k, (img, T) in enumerate(frames[:3]):
         q.track(img, T, k == 0)
     ungated = q.gpu.debug_image(D.IMG_MATCHES)
@@ -248,8 +169,8 @@ def test_matches_image_of_a_frame_with_refused_slots(pair):
 
 @pytest.mark.parametrize("how", ["never_set", "set_to_zero", "set_and_cleared"])
 def test_gate_off_changes_nothing(pair, how):
-    """The no-behaviour-change proof: against frontend_ref.FrontEndRef itself (which knows no gate) on "diagonal_roll"."""
-    p = pair(SC.W, SC.H, K=SC.K, ref=R.FrontEndRef)
+    """The no-behaviour-change proof: against frontend_ref.FrontEndRef with every switch off on "diagonal_roll"."""
+    p = pair(SC.W, SC.H, K=SC.K)
     if how == "set_to_zero":
         p.gpu.set_ref_grad(0.0)
     elif how == "set_and_cleared":

@@ -9,54 +9,11 @@ import pytest
 from tests import fe_debug_ref as D
 from tests import fe_warp_ref as WR
 from tests import fe_warp_scenes as WS
-from tests import frontend_ref as R
 from tests import frontend_scenes as SC
-from tests import test_gpu_fe_gi as TG
-from tests.test_gpu_fe_rg import K_4836
+from tests.fe_pair import K_4836, pair  # noqa: F401  (pair: the fixture)
 
 pytestmark = pytest.mark.gpu
 COSTS = ("ssd", "zssd", "gi")
-
-
-class Pair(TG.Pair):
-    """test_gpu_fe_gi.Pair with the switch and its count."""
-
-    def __init__(self, W, H, ref=None, **kw):
-        super().__init__(W, H, ref=ref or WR.WarpGatesDebugRef, **kw)
-        self.total["warp_refused"] = 0
-        self.warp = 0  # what the device's switch is expected to report
-
-    def set_warp(self, on=True):
-        self.gpu.set_warp(on)
-        self.ref.set_warp(on)
-        self.warp = int(on)
-
-    def set_cost_name(self, cost):
-        if cost == "zssd":
-            self.set_cost()
-        if cost == "gi":
-            self.set_gain_invariant()
-
-    def track(self, img, T, is_pf, img_id=None):
-        tag = "frame %d" % self.frame
-        want = super().track(img, T, is_pf, img_id)
-        refused = self.ref.counts.get("warp_refused", 0)
-        assert self.gpu.info("warp_refused") == refused, tag
-        assert self.gpu.info("warp") == self.warp, tag
-        self.total["warp_refused"] += refused
-        return want
-
-
-@pytest.fixture
-def pair(gpu):
-    made = []
-
-    def make(*a, **kw):
-        made.append(Pair(*a, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
 
 
 def spy_costs(p):
@@ -103,7 +60,7 @@ def test_48x36_under_45_degrees(pair, win, cost):
 
 
 def test_with_the_gradient_gate_and_both_gates(pair):
-    p = pair(WS.W, WS.H, K=WS.K, win_size=7, ref=WR.RgWarpGatesDebugRef)
+    p = pair(WS.W, WS.H, K=WS.K, win_size=7)
     p.set_warp()
     p.set_cost()
     p.set_gates(letterbox=True, max_height=0.05, up=(0, 1, 0))
@@ -116,7 +73,7 @@ def test_with_the_gradient_gate_and_both_gates(pair):
 
 
 def test_with_the_gradient_gate_alone(pair):
-    p = pair(WS.W, WS.H, K=WS.K, win_size=5, ref=WR.RgWarpDebugRef)
+    p = pair(WS.W, WS.H, K=WS.K, win_size=5)
     p.set_warp()
     p.set_ref_grad(12.0)
     for k, (img, T) in enumerate(WS.scene("roll30")[:5]):
@@ -178,8 +135,8 @@ def test_refusal(pair, kind):
 
 @pytest.mark.parametrize("how", ["never_set", "set_and_cleared"])
 def test_switch_off_changes_nothing(pair, how):
-    """The no-behaviour-change proof: against frontend_ref.FrontEndRef itself (which knows no warp at all) on "diagonal_roll"."""
-    p = pair(SC.W, SC.H, K=SC.K, ref=R.FrontEndRef)
+    """The no-behaviour-change proof: against frontend_ref.FrontEndRef with every switch off on "diagonal_roll"."""
+    p = pair(SC.W, SC.H, K=SC.K)
     if how == "set_and_cleared":
         p.gpu.set_warp()
         assert p.gpu.info("warp") == 1
@@ -192,9 +149,9 @@ def test_switch_off_changes_nothing(pair, how):
 
 def test_pure_translation_changes_no_bit_on_the_device(pair):
     """Jq = (256, 0, 0, 256) for every feature: the warped kernel gives what the restatement WITHOUT the switch gives."""
-    p = pair(WS.W, WS.H, K=WS.K, win_size=5, ref=R.FrontEndRef)
+    p = pair(WS.W, WS.H, K=WS.K, win_size=5)
     p.gpu.set_warp()
-    p.warp = 1
+    p.expect["warp"] = 1  # (the restatement runs without the switch)
     for k, (img, T) in enumerate(WS.translation()):
         p.track(img, T, k == 0)
     assert p.total["ok"] >= 200

@@ -11,7 +11,6 @@ import numpy as np
 import pytest
 
 from flame_ros_amd import lib
-from tests import fe_warp_ref as WR
 from tests import fe_warp_scenes as WS
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
@@ -90,7 +89,7 @@ def test_warped_mesh_is_the_library_calls_and_the_restatements(gpu, exe, tmp_pat
     # the restatement over the poses the facade forms, switch on and off
     want = {}
     for warp in (True, False):
-        fe = WR.WarpRef(WS.W, WS.H, WS.K, 4096, 16)
+        fe = R.FrontEndRef(WS.W, WS.H, WS.K, 4096, 16)
         fe.set_warp(warp)
         pr = R.params(win_size=WIN)
         want[warp] = [fe.track(pr, img, 40 + k, T, k == 0) for k, (img, _, _, T) in enumerate(frames)]

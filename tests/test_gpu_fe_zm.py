@@ -6,91 +6,14 @@ import numpy as np
 import pytest
 
 from tests import fe_debug_ref as D
-from tests import fe_zm_ref as Z
 from tests import fe_zm_scenes as ZS
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
+from tests.fe_pair import compare, pair  # noqa: F401  (pair: the fixture)
 
 pytestmark = pytest.mark.gpu
 K_4836 = np.array([140, 0, 23.5, 0, 140, 17.5, 0, 0, 1], np.float32)
 STATUS_KEYS = ("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died")
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def compare(tag, got, want):
-    for k in want:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.shape == w.shape, "%s: %s has shape %s, restatement %s" % (tag, k, g.shape, w.shape)
-        bad = np.flatnonzero((bits(g) != bits(w)).reshape(len(w), -1).any(axis=1)) if len(w) else []
-        assert len(bad) == 0, "%s: %s differs at %s: gpu %s restatement %s" % (tag, k, bad[:5], g[bad[:5]], w[bad[:5]])
-
-
-class Pair:
-    """One GPU handle and one restatement fed the same calls."""
-
-    def __init__(self, W, H, max_features=256, max_poseframes=4, K=R.SCENE_K, ref=None, **kw):
-        from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
-        self.gpu = GpuFrontEnd(W, H, K, max_features, max_poseframes)
-        self.ref = (ref or Z.ZmGatesDebugRef)(W, H, K, max_features, max_poseframes)
-        self.pr, self.pg = R.params(**kw), default_frontend_params(**kw)
-        self.frame = 0
-        self.total = dict(held=0, refused=0, emitted=0)
-        self.total.update({k: 0 for k in STATUS_KEYS})
-        self.record = []  # per frame: what the GPU gave (features, state, searches)
-
-    def close(self):
-        self.gpu.close()
-
-    def set_cost(self, zero_mean=True):
-        self.gpu.set_cost(zero_mean)
-        self.ref.set_cost(zero_mean)
-        assert self.gpu.info("cost_mode") == self.ref.cost_mode
-
-    def set_gates(self, **kw):
-        self.gpu.set_gates(**kw)
-        self.ref.set_gates(**kw)
-
-    def track(self, img, T, is_pf, img_id=None):
-        img_id = self.frame if img_id is None else img_id
-        want = self.ref.track(self.pr, img, img_id, T, is_pf)
-        got = self.gpu.track(self.pg, img, img_id, T, is_pf)
-        tag = "frame %d" % self.frame
-        compare(tag, got, want)
-        state = self.gpu.state()
-        compare(tag + " state", state, self.ref.state())
-        searches = None
-        if hasattr(self.ref, "searches"):
-            searches = self.gpu.searches()
-            compare(tag + " searches", searches, self.ref.searches())
-        for st, key in enumerate(STATUS_KEYS):
-            assert self.gpu.info(key) == self.ref.counts.get(st, 0), (tag, key)
-            self.total[key] += self.ref.counts.get(st, 0)
-        assert self.gpu.info("emitted") == len(want["slot"]) and self.gpu.info("detections_dropped") == self.ref.dropped
-        assert self.gpu.info("live") == int(self.ref.alive.sum())
-        held, refused = getattr(self.ref, "held", 0), getattr(self.ref, "refused", 0)
-        assert self.gpu.info("held_height") == held and self.gpu.info("refused_letterbox") == refused, tag
-        self.total["held"] += held
-        self.total["refused"] += refused
-        self.total["emitted"] += len(want["slot"])
-        self.record.append((got, state, searches))
-        self.frame += 1
-        return want
-
-
-@pytest.fixture
-def pair(gpu):
-    made = []
-
-    def make(*a, **kw):
-        made.append(Pair(*a, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
 
 
 OFFSETS = ZS.random_offsets(7)
@@ -224,8 +147,8 @@ def test_matches_image_of_a_zssd_frame(pair):
 
 @pytest.mark.parametrize("how", ["never_set", "set_to_ssd", "zssd_and_back"])
 def test_ssd_mode_changes_nothing(pair, how):
-    """The no-behaviour-change proof: against frontend_ref.FrontEndRef itself (which knows no cost mode) on "diagonal_roll"."""
-    p = pair(SC.W, SC.H, K=SC.K, ref=R.FrontEndRef)
+    """The no-behaviour-change proof: against frontend_ref.FrontEndRef with every switch off on "diagonal_roll"."""
+    p = pair(SC.W, SC.H, K=SC.K)
     if how == "set_to_ssd":
         p.gpu.set_cost(zero_mean=False)
     elif how == "zssd_and_back":

@@ -8,70 +8,9 @@ import pytest
 
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
+from tests.fe_pair import pair  # noqa: F401  (pair: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def compare(tag, got, want):
-    for k in want:
-        g, w = np.asarray(got[k]), np.asarray(want[k])
-        assert g.shape == w.shape, "%s: %s has shape %s, restatement %s" % (tag, k, g.shape, w.shape)
-        bad = np.flatnonzero((bits(g) != bits(w)).reshape(len(w), -1).any(axis=1)) if len(w) else []
-        assert len(bad) == 0, "%s: %s differs at %s: gpu %s restatement %s" % (tag, k, bad[:5], g[bad[:5]], w[bad[:5]])
-
-
-class Pair:
-    """One GPU handle and one restatement fed the same calls."""
-
-    def __init__(self, W, H, max_features=256, max_poseframes=4, K=R.SCENE_K, pitch=None, **kw):
-        from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
-        self.gpu = GpuFrontEnd(W, H, K, max_features, max_poseframes)
-        self.ref = R.FrontEndRef(W, H, K, max_features, max_poseframes)
-        self.pr, self.pg = R.params(**kw), default_frontend_params(**kw)
-        self.pitch, self.frame = pitch, 0
-
-    def close(self):
-        self.gpu.close()
-
-    def track(self, img, T, is_pf, img_id=None):
-        img_id = self.frame if img_id is None else img_id
-        gimg = img
-        if self.pitch:  # rows `pitch` bytes apart, the image starting at an odd address
-            buf = np.full(img.shape[0] * self.pitch + 1, 0xAB, np.uint8)
-            gimg = np.lib.stride_tricks.as_strided(buf[1:], img.shape, (self.pitch, 1))
-            gimg[...] = img
-        want = self.ref.track(self.pr, img, img_id, T, is_pf)
-        got = self.gpu.track(self.pg, gimg, img_id, T, is_pf)
-        tag = "frame %d" % self.frame
-        compare(tag, got, want)
-        self.check_state(tag)
-        for st, key in enumerate(("ok", "no_parallax", "outside", "bad_match", "ambiguous", "new", "died")):
-            assert self.gpu.info(key) == self.ref.counts.get(st, 0), (tag, key)
-        assert self.gpu.info("emitted") == len(want["slot"]) and self.gpu.info("detections_dropped") == self.ref.dropped
-        self.frame += 1
-        return want
-
-    def check_state(self, tag):
-        compare(tag + " state", self.gpu.state(), self.ref.state())
-        assert self.gpu.info("live") == int(self.ref.alive.sum())
-        assert self.gpu.info("poseframes") == sum(self.ref.pf_used)
-
-
-@pytest.fixture
-def pair(gpu):
-    made = []
-
-    def make(*a, **kw):
-        made.append(Pair(*a, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
 
 
 def test_odd_width_pitch_and_partial_cells(pair):

@@ -9,7 +9,7 @@ import pytest
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
 from tests import ingest_ref as IR
-from tests.test_gpu_frontend import Pair, compare
+from tests.fe_pair import compare, pair  # noqa: F401  (pair: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -130,18 +130,6 @@ def test_rectify_leaves_state_and_tracking_untouched(pair):
     same(p.gpu.image(), before, "image() after rectify")
     p.track(b[0], b[1], False)
     assert p.ref.counts.get(R.OK, 0) >= 30
-
-
-@pytest.fixture
-def pair(gpu):
-    made = []
-
-    def make(*a, **kw):
-        made.append(Pair(*a, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
 
 
 TRACK_D = (-0.28, 0.07, 0.0002, 0.00002, 0.0)

@@ -85,7 +85,7 @@ def test_sequence_through_the_gpu_tracker(gpu, exe, sequence, tmp_path):
     assert p.returncode == 3, (p.returncode, p.stdout, p.stderr)  # (the first frames fail: nothing is under the variance gate yet)
     rows = rows_of(p.stdout)
     assert len(rows) == FRAMES
-    ref = D.DebugRef(SC.W, SC.H, np.array(SC.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
+    ref = R.FrontEndRef(SC.W, SC.H, np.array(SC.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
     pr = R.params()
     oks = []
     for k, (r, (img, _)) in enumerate(zip(rows, frames)):

@@ -38,7 +38,7 @@ def test_sequence_with_gates(gpu, exe, sequence, flags, kw):  # noqa: F811
     assert p.returncode == 3, (p.returncode, p.stdout, p.stderr)  # (the first frames fail: nothing is under the variance gate yet)
     rows, counts = rows_of(p.stdout), gate_counts(p.stdout)
     assert len(rows) == FRAMES and None not in counts
-    ref = G.GatesRef(SC.W, SC.H, np.array(SC.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
+    ref = R.FrontEndRef(SC.W, SC.H, np.array(SC.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
     ref.set_gates(**kw)
     pr = R.params()
     oks, held = [], 0

@@ -9,7 +9,6 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import fe_gi_ref as GI
 from tests import fe_gi_scenes as GS
 from tests import fe_zm_scenes as ZS
 from tests import frontend_ref as R
@@ -46,7 +45,7 @@ def test_sequence_with_the_flag(gpu, exe, sequences):  # noqa: F811
         rows = rows_of(p.stdout)
         assert len(rows) == FRAMES and switches(p.stdout) == [1] * FRAMES
         assert all(l.split()[-2:] == ["gain_invariant", "1"] for l in p.stdout.splitlines() if l.startswith("frame "))  # (appended)
-        ref = GI.GiRef(ZS.W, ZS.H, np.array(ZS.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
+        ref = R.FrontEndRef(ZS.W, ZS.H, np.array(ZS.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
         ref.set_gain_invariant()
         pr = R.params(win_size=WIN)
         oks = []

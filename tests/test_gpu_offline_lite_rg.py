@@ -41,7 +41,7 @@ def test_sequence_with_the_gate(gpu, exe, sequence):  # noqa: F811
     assert p.returncode == 3, (p.returncode, p.stdout, p.stderr)  # (the first frames fail: nothing is under the variance gate yet)
     rows, fails = rows_of(p.stdout), fail_ref_grad(p.stdout)
     assert len(rows) == FRAMES == len(fails)
-    ref = RG.RgRef(ZS.W, ZS.H, np.array(ZS.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
+    ref = R.FrontEndRef(ZS.W, ZS.H, np.array(ZS.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
     ref.set_ref_grad(MIN_GRAD)
     pr = R.params(win_size=WIN)
     oks, want = [], []

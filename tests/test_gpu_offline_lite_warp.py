@@ -8,7 +8,6 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import fe_warp_ref as WR
 from tests import fe_warp_scenes as WS
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
@@ -50,7 +49,7 @@ def fail_warp(stdout):
 
 
 def restatement(rows, frames, warp):
-    ref = WR.WarpRef(WS.W, WS.H, np.array(WS.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
+    ref = R.FrontEndRef(WS.W, WS.H, np.array(WS.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
     ref.set_warp(warp)
     pr = R.params(win_size=WIN)
     out = []

@@ -8,7 +8,6 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import fe_zm_ref as Z
 from tests import fe_zm_scenes as ZS
 from tests import frontend_ref as R
 from tests import frontend_scenes as SC
@@ -64,7 +63,7 @@ def test_sequence_with_zero_mean(gpu, exe, sequences):  # noqa: F811
         assert p.returncode == 3, (p.returncode, p.stdout, p.stderr)  # (the first frames fail: nothing is under the variance gate yet)
         rows = rows_of(p.stdout)
         assert len(rows) == FRAMES and cost_modes(p.stdout) == [1] * FRAMES
-        ref = Z.ZmRef(ZS.W, ZS.H, np.array(ZS.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
+        ref = R.FrontEndRef(ZS.W, ZS.H, np.array(ZS.K, np.float32), 4096, 16)  # flame::GpuFrontEnd's slots and ring
         ref.set_cost()
         pr = R.params(win_size=WIN)
         oks = []

@@ -34,7 +34,7 @@ def run(frames, win, min_grad, device):
         fe, p = GpuFrontEnd(ZS.W, ZS.H, ZS.K, 256, 4), default_frontend_params(win_size=win)
         counts = lambda: (fe.info("fail_ref_grad"), sum(fe.info(k) for k in ("ok", "bad_match", "ambiguous")) + fe.info("fail_ref_grad"))  # noqa: E731
     else:
-        fe, p = RG.RgRef(ZS.W, ZS.H, ZS.K, 256, 4), R.params(win_size=win)
+        fe, p = R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4), R.params(win_size=win)
         counts = lambda: (fe.counts.get(RG.REF_GRAD, 0), sum(fe.counts.get(k, 0) for k in (R.OK, R.BAD_MATCH, R.AMBIGUOUS, RG.REF_GRAD)))  # noqa: E731
     fe.set_ref_grad(min_grad)
     for k, (img, T) in enumerate(frames):

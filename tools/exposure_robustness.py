@@ -14,7 +14,7 @@ emitted features of the last frame and the median relative inverse-depth error o
 
     python tools/exposure_robustness.py [--smooth] [--gain-table] [--restatement]
 
---restatement runs tests/fe_gi_ref.py (fe_zm_ref.py plus the gain-invariant cost) on the CPU instead of the device (the device equals
+--restatement runs tests/frontend_ref.py with the gain-invariant cost of tests/fe_gi_ref.py on the CPU instead of the device (the device equals
 it bit for bit: tests/test_gpu_fe_zm.py, tests/test_gpu_fe_gi.py).
 """
 import argparse
@@ -47,9 +47,8 @@ def frames_of(smooth, gain, b):
 def run(frames, win, zero_mean, restatement, gain_invariant=False):
     from tests import fe_zm_scenes as ZS
     if restatement:
-        from tests import fe_gi_ref as GI
         from tests import frontend_ref as R
-        fe, p = GI.GiRef(ZS.W, ZS.H, ZS.K, 256, 4), R.params(win_size=win)
+        fe, p = R.FrontEndRef(ZS.W, ZS.H, ZS.K, 256, 4), R.params(win_size=win)
         bad = lambda: fe.counts.get(R.BAD_MATCH, 0)  # noqa: E731
     else:
         from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params

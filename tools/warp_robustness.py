@@ -28,7 +28,6 @@ SCENES = [("roll 0", (0.0, 0.0)), ("roll 10", (10.0, 0.0)), ("roll 20", (20.0, 0
 
 
 def run(frames, win, cost, warp, device):
-    from tests import fe_warp_ref as WR
     from tests import fe_warp_scenes as WS
     from tests import frontend_ref as R
     if device:
@@ -36,7 +35,7 @@ def run(frames, win, cost, warp, device):
         fe, p = GpuFrontEnd(WS.W, WS.H, WS.K, 256, 4), default_frontend_params(win_size=win)
         refused = lambda: fe.info("warp_refused")  # noqa: E731
     else:
-        fe, p = WR.WarpRef(WS.W, WS.H, WS.K, 256, 4), R.params(win_size=win)
+        fe, p = R.FrontEndRef(WS.W, WS.H, WS.K, 256, 4), R.params(win_size=win)
         refused = fe.warp_refused
     fe.set_cost(cost == "zssd")
     fe.set_gain_invariant(cost == "gi")
