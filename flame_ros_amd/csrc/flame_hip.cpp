@@ -526,7 +526,7 @@ struct flame_hip_graph {
 
 extern "C" {
 
-int flame_hip_version(void) { return 412; }  // (412: the front end's warped matching window, flame_hip_frontend_set_warp; 411: the front end's gain-invariant matching cost, flame_hip_frontend_set_gain_invariant; 410: the front end's reference-patch gradient gate, flame_hip_frontend_set_ref_grad; 409: the front end's matching cost, flame_hip_frontend_set_cost; 408: the front end's gates, flame_hip_frontend_set_gates; 407: the front end's search record and debug images, flame_hip_frontend_searches / _debug_image; 406: the ingest stage, flame_hip_frontend_set_camera / _track_raw / _rectify / _image; 405: the evaluate stage, flame_hip_photo_reference / _photo_error / _truth_stats; 404: the prediction stage, flame_hip_predict / _predict_map; 403: the feature front end, flame_hip_frontend_*; 402, r06: halo view, peer transport, local communicator, handle options instead of environment switches)
+int flame_hip_version(void) { return 413; }  // (413: the front end's hand-over of an evicted pose frame's features, flame_hip_frontend_set_carry; 412: the front end's warped matching window, flame_hip_frontend_set_warp; 411: the front end's gain-invariant matching cost, flame_hip_frontend_set_gain_invariant; 410: the front end's reference-patch gradient gate, flame_hip_frontend_set_ref_grad; 409: the front end's matching cost, flame_hip_frontend_set_cost; 408: the front end's gates, flame_hip_frontend_set_gates; 407: the front end's search record and debug images, flame_hip_frontend_searches / _debug_image; 406: the ingest stage, flame_hip_frontend_set_camera / _track_raw / _rectify / _image; 405: the evaluate stage, flame_hip_photo_reference / _photo_error / _truth_stats; 404: the prediction stage, flame_hip_predict / _predict_map; 403: the feature front end, flame_hip_frontend_*; 402, r06: halo view, peer transport, local communicator, handle options instead of environment switches)
 
 const char* flame_hip_strerror(int code) {
   switch (code) {

@@ -11,8 +11,9 @@
 // their place while it is on.  flame_hip_frontend_set_ref_grad records the reference-patch gradient
 // gate; while it is on every frame forms the epipole table behind the pose table and runs the tracker's gated instantiation.
 // flame_hip_frontend_set_warp records the warped-window switch; while it is on every frame runs the tracker's warped instantiation
-// (it reads the pose table and the intrinsics the frame holds anyway).  Reads
-// no environment variable.
+// (it reads the pose table and the intrinsics the frame holds anyway).  flame_hip_frontend_set_carry records the hand-over switch;
+// while it is on a pose frame that takes a ring slot in use goes into the extra image slot, no kill runs, k_fe_carry runs behind
+// k_fe_compact and the image is copied into the ring slot on the stream.  Reads no environment variable.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -81,6 +82,8 @@ struct flame_hip_frontend {
   int32_t gain_invariant = 0;
   // the warped window (set_warp): no state depends on it either
   int32_t warp = 0;
+  // the hand-over (set_carry): read by the evicting pose frames alone; no state depends on it either
+  int32_t carry = 0;
   // reference-patch gradient gate (set_ref_grad): 0 = off; no state depends on it either
   float min_epi_grad = 0.f;
 };
@@ -344,16 +347,22 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
     f.det = fe->d_det;
   }
   f.cell_held = reinterpret_cast<int32_t*>(fe->d_cell_key + ncells);  // (behind this frame's keys: one clear covers both)
-  // a pose frame takes the ring's next slot; the features of the pose frame it overwrites die before tracking
+  // a pose frame takes the ring's next slot; the features of the pose frame it overwrites die before tracking -- or, with the
+  // hand-over on (DESIGN.md 5.3 "Hand-over"), are tracked against the new image once more: the image goes into the extra slot, the
+  // ring slot keeps the old pose frame's image and record through the frame, and k_fe_carry hands the emitted ones over
   int32_t cur = fe->max_poseframes;  // the extra image slot
-  bool overwrote = false;
+  int32_t img_slot = cur;            // where this frame's image goes
+  bool overwrote = false, carry = false;
   if (is_poseframe) {
     cur = (int32_t)(fe->pf_added % fe->max_poseframes);
     overwrote = fe->pf_used[cur] != 0;
-    fe->pf_used[cur] = 0;
+    carry = overwrote && fe->carry != 0;
+    if (carry) overwrote = false;
+    else { fe->pf_used[cur] = 0; img_slot = cur; }
   }
+  uint8_t* const d_cur = fe->d_imgs + (size_t)img_slot * npix;
   f.cur_pf = cur;
-  f.cur = fe->d_imgs + (size_t)cur * npix;
+  f.cur = d_cur;
   for (int p = 0; p < fe->max_poseframes; ++p) {
     if (fe->pf_used[p]) pose_record(fe->fx, fe->fy, fe->cx, fe->cy, T_world_cam, &fe->pf_T[12 * (size_t)p], &fe->h_poses[p]);
     else std::memset(&fe->h_poses[p], 0, sizeof(FePose));
@@ -369,11 +378,11 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
   if (raw) {
     stage_raw(fe, img, pitch);
     FE_HIP(hipEventRecord(fe->ev0, s));
-    if (const int rc = queue_ingest(fe, fe->d_imgs + (size_t)cur * npix)) return rc;
+    if (const int rc = queue_ingest(fe, d_cur)) return rc;
   } else {
     for (int32_t y = 0; y < H; ++y) std::memcpy(fe->h_img + (size_t)y * W, img + (size_t)y * pitch, (size_t)W);
     FE_HIP(hipEventRecord(fe->ev0, s));
-    FE_HIP(hipMemcpyAsync(fe->d_imgs + (size_t)cur * npix, fe->h_img, npix, hipMemcpyHostToDevice, s));
+    FE_HIP(hipMemcpyAsync(d_cur, fe->h_img, npix, hipMemcpyHostToDevice, s));
   }
   FE_HIP(hipMemcpyAsync(fe->d_poses, fe->h_poses, (ref_grad ? kPoseBytes : sizeof(FePose)) * (size_t)fe->max_poseframes, hipMemcpyHostToDevice, s));
   FE_HIP(hipMemsetAsync(fe->d_cell_key, 0xFF, (sizeof(unsigned long long) + sizeof(int32_t)) * (size_t)ncells, s));
@@ -382,6 +391,12 @@ static int run_track(flame_hip_frontend* fe, const flame_hip_frontend_params* pa
   fe_launch_track(s, f, cost, ref_grad, fe->warp != 0);
   if (is_poseframe) fe_launch_detect(s, f);
   fe_launch_compact(s, f);
+  if (carry) {  // the old pose frame's emitted features move to the new one, the rest of them die; then the ring slot takes the image
+    fe_launch_carry(s, f);
+    FE_HIP(hipGetLastError());
+    FE_HIP(hipMemcpyAsync(fe->d_imgs + (size_t)cur * npix, d_cur, npix, hipMemcpyDeviceToDevice, s));
+    f.cur = fe->d_imgs + (size_t)cur * npix;  // (the same bytes: the extra slot is free again)
+  }
   FE_HIP(hipGetLastError());
   FE_HIP(hipMemcpyAsync(fe->h_counts, fe->d_counts, sizeof(int32_t) * kFeCounts, hipMemcpyDeviceToHost, s));
   FE_HIP(hipEventRecord(fe->ev1, s));
@@ -494,6 +509,12 @@ int flame_hip_frontend_set_gain_invariant(flame_hip_frontend* fe, int32_t on) {
 int flame_hip_frontend_set_warp(flame_hip_frontend* fe, int32_t on) {
   if (!fe || (on != 0 && on != 1)) return FLAME_HIP_ERR_ARG;
   fe->warp = on;  // takes effect with the next frame
+  return 0;
+}
+
+int flame_hip_frontend_set_carry(flame_hip_frontend* fe, int32_t on) {
+  if (!fe || (on != 0 && on != 1)) return FLAME_HIP_ERR_ARG;
+  fe->carry = on;  // takes effect with the next pose frame that takes a ring slot in use
   return 0;
 }
 
@@ -663,6 +684,9 @@ int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* va
   if (!std::strcmp(key, "gain_invariant")) { *value = fe->gain_invariant; return 0; }
   if (!std::strcmp(key, "warp")) { *value = fe->warp; return 0; }
   if (!std::strcmp(key, "warp_refused")) { *value = fe->counts[13]; return 0; }
+  if (!std::strcmp(key, "carry")) { *value = fe->carry; return 0; }
+  if (!std::strcmp(key, "carried")) { *value = fe->counts[14]; return 0; }
+  if (!std::strcmp(key, "carry_lost")) { *value = fe->counts[15]; return 0; }
   if (!std::strcmp(key, "ref_grad")) { *value = fe->min_epi_grad > 0.f ? 1 : 0; return 0; }
   if (!std::strcmp(key, "fail_ref_grad")) { *value = fe->counts[12]; return 0; }
   if (!std::strcmp(key, "held_height")) { *value = fe->counts[10]; return 0; }

@@ -17,7 +17,8 @@ enum { kFeOk = 0, kFeNoParallax = 1, kFeOutside = 2, kFeBadMatch = 3, kFeAmbiguo
 constexpr int kFeCounts = 16;  // counts[]: 0 = emitted, 1 = live, 2 + status = features of that status (0..6), 9 = detections dropped (no free slot),
                                // 10 = features held by the height gate, 11 = projections refused by the letterbox,
                                // 12 = features of status kFeRefGrad (2 + 7 is taken),
-                               // 13 = features the warped window refused (they are among the kFeOutside ones as well)
+                               // 13 = features the warped window refused (they are among the kFeOutside ones as well),
+                               // 14 / 15 = features of the evicted pose frame the hand-over carried / lost (k_fe_carry)
 
 // A = K R and c = K t of T_cur_ref, rounded once to float32 on the host (one record per pose-frame ring slot)
 struct FePose {
@@ -124,6 +125,8 @@ enum { kFeCostSsd = 0, kFeCostZssd = 1, kFeCostGi = 2 };
 void fe_launch_track(hipStream_t s, const FeFrame& f, int cost, bool ref_grad, bool warp);
 void fe_launch_detect(hipStream_t s, const FeFrame& f);
 void fe_launch_compact(hipStream_t s, const FeFrame& f);
+// the hand-over behind k_fe_compact of an evicting pose frame (DESIGN.md 5.3 "Hand-over"): the evicted ring slot is f.cur_pf; counts[14], counts[15]
+void fe_launch_carry(hipStream_t s, const FeFrame& f);
 
 // frontend_debug.hip: the Detections / Matches debug images (DESIGN.md 5.3 "Debug images"), BGR8 with dense rows (3 W bytes) into
 // `bgr`, from the frame's record in `f` (status, kstar, seg, steps; the first n_out records of f.out) on stream s.

@@ -1,6 +1,7 @@
 // flame_ros_amd/csrc/frontend.hip -- kernels of the feature front end (gfx950): epipolar inverse-depth tracking, one wavefront
 // per live feature with the lanes over the samples of its search (k_fe_track); gradient-maximum detection, one wavefront per
-// grid cell (k_fe_detect); slot assignment of the detections and compaction of the emitted features (k_fe_compact).
+// grid cell (k_fe_detect); slot assignment of the detections and compaction of the emitted features (k_fe_compact); the hand-over
+// of an evicted pose frame's features to the pose frame that takes its ring slot, one thread per slot (k_fe_carry).
 //
 // Arithmetic contract (DESIGN.md "Feature front end"): float32 with + - x / sqrtf floorf ceilf only, every operation rounded
 // on its own (-ffp-contract=off, NO fmaf here: the restatement in tests/frontend_ref.py is NumPy, which has none), image costs
@@ -602,8 +603,40 @@ __global__ __launch_bounds__(1024) void k_fe_compact(FeFrame f) {
   }
 }
 
+// The hand-over (DESIGN.md 5.3 "Hand-over", flame_hip_frontend_set_carry): behind k_fe_compact of a pose frame that takes the ring
+// slot f.cur_pf while the slot is in use.  One thread per slot; the old pose frame's features are the live slots of that ring slot
+// that are not NEW.  One of them that this frame emitted (status OK or NO_PARALLAX, winner of its cell) at a pixel where k_fe_detect
+// could have put a detection is carried: the emitted projection, rounded to the pixel, becomes its reference pixel and its prior --
+// copies of the frame's own bits, two floorf, integer compares.  Every other one dies here (alive alone is written).
+__global__ __launch_bounds__(256) void k_fe_carry(FeFrame f) {
+  const int slot = blockIdx.x * 256 + threadIdx.x;
+  if (slot >= f.max_features) return;
+  if (!f.alive[slot] || f.pf[slot] != f.cur_pf) return;
+  const int status = f.status[slot];
+  if (status == kFeNew) return;
+  bool carried = false;
+  const int cell = f.cell_of[slot];
+  if ((status == kFeOk || status == kFeNoParallax) && cell >= 0 &&
+      (unsigned int)(f.cell_key[cell] & 0xFFFFFFFFull) == (unsigned int)slot) {
+    const float4 pr = f.proj[slot];
+    const int ur = (int)floorf(pr.x + 0.5f), vr = (int)floorf(pr.y + 0.5f), m = (f.win >> 1) + 1;
+    if (ur >= m && ur < f.W - m && vr >= max(m, f.gates.y_lo) && vr < min(f.H - m, f.gates.y_hi)) {
+      f.u[slot] = ur;
+      f.v[slot] = vr;
+      f.mu[slot] = pr.z;
+      f.var[slot] = pr.w;
+      carried = true;
+    }
+  }
+  if (!carried) f.alive[slot] = 0;
+  atomicAdd(&f.counts[carried ? 14 : 15], 1);
+}
+
 }  // namespace
 
+void fe_launch_carry(hipStream_t s, const FeFrame& f) {
+  hipLaunchKernelGGL(k_fe_carry, dim3((f.max_features + 255) / 256), dim3(256), 0, s, f);
+}
 void fe_launch_kill(hipStream_t s, const FeFrame& f, unsigned long long valid_mask) {
   hipLaunchKernelGGL(k_fe_kill, dim3((f.max_features + 255) / 256), dim3(256), 0, s, f, valid_mask);
 }

@@ -147,6 +147,14 @@ class GpuFrontEnd:
         May change between any two frames."""
         _l.check(self._lib.flame_hip_frontend_set_warp(self._h, 1 if on else 0), "flame_hip_frontend_set_warp")
 
+    def set_carry(self, on=True):
+        """The hand-over for the pose frames to come: when a pose frame takes a ring slot that is in use, the features of the pose
+        frame it evicts are tracked against the new image once more instead of dying; those the frame emits (status OK or
+        NO_PARALLAX, winner of their cell) at a pixel where a detection could sit are re-anchored in the new pose frame at that
+        pixel, with the emitted inverse depth and variance as their prior; the others die behind the frame.  For cameras that
+        hover.  Info keys "carried", "carry_lost" (of the last frame).  May change between any two frames."""
+        _l.check(self._lib.flame_hip_frontend_set_carry(self._h, 1 if on else 0), "flame_hip_frontend_set_carry")
+
     def set_ref_grad(self, min_grad):
         """The reference-patch gradient gate of the frames to come: a feature whose reference window has a root-mean-square grey
         gradient below `min_grad` ALONG its epipolar line (an edge parallel to the line: the aperture problem) is not searched and

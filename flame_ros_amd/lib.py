@@ -135,6 +135,7 @@ SYMBOLS = {
     "flame_hip_frontend_set_ref_grad": (C.c_int, [_VP, C.c_float]),
     "flame_hip_frontend_set_gain_invariant": (C.c_int, [_VP, _I32]),
     "flame_hip_frontend_set_warp": (C.c_int, [_VP, _I32]),
+    "flame_hip_frontend_set_carry": (C.c_int, [_VP, _I32]),
     "flame_hip_debug_plan_array": (_I64, [_VP, C.c_char_p, _VP, _I64]),
     "flame_hip_strerror": (C.c_char_p, [C.c_int]),
     "flame_hip_version": (C.c_int, []),

@@ -45,6 +45,12 @@
 // Params::warp_matching_window (this build's own switch: the matching window follows the camera's roll and change of distance
 // against the pose frame); setWarp() changes it later, between any two frames.  With the switch off no call is made at all and
 // `num_fail_warp` stays unset.  A refusal lands in lastError() and fails every track() until a call succeeds.
+//
+// HAND-OVER (flame_hip.h, flame_hip_frontend_set_carry; DESIGN.md 5.3 "Hand-over"): the constructor honours Params::carry_features
+// (this build's own switch: when a pose frame takes a ring slot in use, the features of the pose frame it evicts that the frame
+// still emits are re-anchored in the new pose frame instead of dying); setCarry() changes it later, between any two frames.  With
+// the switch off no call is made at all and `num_carried` / `num_carry_lost` stay unset.  A refusal lands in lastError() and fails
+// every track() until a call succeeds.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -96,6 +102,11 @@ class GpuFrontEnd {
     if (handle_ && params.warp_matching_window) {  // (off: no call at all)
       const int before = last_error_;
       setWarp(true);
+      if (before) last_error_ = before;  // (an earlier refusal stays what lastError() shows)
+    }
+    if (handle_ && params.carry_features) {  // (off: no call at all)
+      const int before = last_error_;
+      setCarry(true);
       if (before) last_error_ = before;  // (an earlier refusal stays what lastError() shows)
     }
   }
@@ -198,6 +209,18 @@ class GpuFrontEnd {
   }
   bool warp() const { return warp_; }
 
+  // The hand-over of the pose frames to come (true): a pose frame that takes a ring slot in use re-anchors the evicted pose frame's
+  // features that it emits in itself, the others die behind the frame; false (the default): they all die before it.  May change
+  // between any two frames.  false (lastError()) when the library refuses; track() then fails until a call succeeds.
+  bool setCarry(bool on) {
+    if (!handle_) return false;
+    carry_error_ = flame_hip_frontend_set_carry(handle_, on ? 1 : 0);
+    last_error_ = carry_error_;
+    if (!carry_error_) carry_ = on;
+    return carry_error_ == 0;
+  }
+  bool carry() const { return carry_; }
+
   // The ingest stage alone (flame_hip_frontend_rectify): `out` becomes the width x height rectified image of `raw`; the
   // feature state is untouched.
   bool rectify(const Image1b& raw, Image1b* out) {
@@ -244,6 +267,7 @@ class GpuFrontEnd {
     if (gain_invariant_error_) return fail(gain_invariant_error_);
     if (ref_grad_error_) return fail(ref_grad_error_);  // (nor a refused gradient gate)
     if (warp_error_) return fail(warp_error_);          // (nor a refused warp switch)
+    if (carry_error_) return fail(carry_error_);        // (nor a refused hand-over switch)
     rectified_valid_ = false;
     const int rows = have_camera_ ? raw_height_ : height_, cols = have_camera_ ? raw_width_ : width_;
     if (!in.img || !out || in.img->rows != rows || in.img->cols != cols) return fail(FLAME_HIP_ERR_ARG);
@@ -282,7 +306,8 @@ class GpuFrontEnd {
   // (flame_hip_frontend_info): features whose idepth was updated, features that died of too many dropouts, ambiguous matches,
   // matches above the cost threshold.  `num_fail_max_var` is Flame's own (its variance gate); `num_fail_ref_patch_grad` is
   // the features the reference-patch gradient gate refused and is set only while that gate is on (it is off by default: unset);
-  // `num_fail_warp` is the features the warped window refused and is set only while that switch is on.
+  // `num_fail_warp` is the features the warped window refused and is set only while that switch is on; `num_carried` and
+  // `num_carry_lost` are the evicted pose frame's features the frame handed over / lost and are set only while the hand-over is on.
   void reportStats(utils::StatsTracker* stats) const {
     if (!handle_ || !stats) return;
     static const char* const kKeys[4][2] = {{"num_idepth_updates", "ok"}, {"num_fail_max_dropouts", "died"},
@@ -302,6 +327,10 @@ class GpuFrontEnd {
     }
     if (flame_hip_frontend_info(handle_, "warp", &g) == 0 && g != 0) {
       if (flame_hip_frontend_info(handle_, "warp_refused", &v) == 0) stats->set("num_fail_warp", static_cast<double>(v));
+    }
+    if (flame_hip_frontend_info(handle_, "carry", &g) == 0 && g != 0) {
+      if (flame_hip_frontend_info(handle_, "carried", &v) == 0) stats->set("num_carried", static_cast<double>(v));
+      if (flame_hip_frontend_info(handle_, "carry_lost", &v) == 0) stats->set("num_carry_lost", static_cast<double>(v));
     }
   }
 
@@ -338,6 +367,8 @@ class GpuFrontEnd {
   int ref_grad_error_ = 0;  // ... and to the last gradient gate
   bool warp_ = false;
   int warp_error_ = 0;      // ... and to the last warp switch
+  bool carry_ = false;
+  int carry_error_ = 0;     // ... and to the last hand-over switch
   flame_hip_frontend* handle_ = nullptr;
   int last_error_ = 0;
 };

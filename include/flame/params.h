@@ -4,7 +4,9 @@
 // src/flame_offline_tum.cc:158-249, src/flame_offline_asl.cc, src/flame_nodelet.cc:220-330);
 // defaults are the values of cfg/flame_offline_tum.yaml.  The regulariser / triangle-filter fields
 // drive the GPU tail; min_grad_mag, detection_win_size, max_dropouts, zparams.win_size and
-// zparams.epipolar_line_var drive the GPU feature front end (flame/gpu_frontend.h); the rest are
+// zparams.epipolar_line_var drive the GPU feature front end (flame/gpu_frontend.h), and so do this
+// build's own switches (zero_mean_matching, gain_invariant_matching, min_epipolar_grad,
+// warp_matching_window, carry_features: all off by default); the rest are
 // carried so the frontends compile and can be forwarded to another feature pipeline unchanged.
 #pragma once
 
@@ -97,6 +99,14 @@ struct Params {
   // fails like one outside the image; `num_fail_warp` counts them.  Off by default: with it off the front end makes exactly the
   // calls it made before and the key stays unset.  Any other registered FrontEnd gets the field carried and has to honour it itself.
   bool warp_matching_window = false;
+  // (this build's own) true = the hand-over of flame::GpuFrontEnd's tracker (gpu_frontend.h; DESIGN.md 5.3 "Hand-over";
+  // flame_hip_frontend_set_carry): when a pose frame takes a slot of the pose-frame ring that is in use, the features of the pose
+  // frame it evicts are tracked against the new image once more; those the frame emits at a pixel where a detection could sit are
+  // re-anchored in the new pose frame with the emitted inverse depth and variance, the others die behind the frame -- so that a
+  // camera that hovers keeps its converged features.  `num_carried` / `num_carry_lost` count them.  Off by default: with it off the
+  // front end makes exactly the calls it made before and the keys stay unset.  Any other registered FrontEnd gets the field carried
+  // and has to honour it itself.
+  bool carry_features = false;
   // features (:209-231)
   // do_letterbox ("Process only middle third of image"): honoured by flame::GpuFrontEnd (gpu_frontend.h; DESIGN.md 5.3 "Gates")
   bool do_letterbox = false;

@@ -558,7 +558,9 @@ int flame_hip_frontend_prune(flame_hip_frontend* fe, int32_t n, const uint32_t* 
  * call uploaded); "gates" (bit 0 = letterbox, bit 1 = height band: what _set_gates last set), "held_height" / "refused_letterbox"
  * (features of the last frame the height band held / whose projection the letterbox refused); "cost_mode" (FLAME_HIP_FE_COST_*:
  * what _set_cost last set); "gain_invariant" (what _set_gain_invariant last set); "ref_grad" (1 while the gate of _set_ref_grad is on), "fail_ref_grad" (features of the last frame with
- * status REF_GRAD); "warp" (what _set_warp last set), "warp_refused" (features of the last frame the warped window refused) */
+ * status REF_GRAD); "warp" (what _set_warp last set), "warp_refused" (features of the last frame the warped window refused);
+ * "carry" (what _set_carry last set), "carried" / "carry_lost" (features of the evicted pose frame that the last frame handed over
+ * to the new one / that died at the hand-over; both 0 for a frame that evicted nothing or ran with the switch off) */
 int flame_hip_frontend_info(flame_hip_frontend* fe, const char* key, int64_t* value);
 /* Debug/test hook: every slot's state (max_features entries each; any pointer may be NULL): alive, reference pixel (u, v),
  * ring slot of its pose frame, prior (mu, var) in the pose frame, dropout counter, last status (-1 = free), last best sample. */
@@ -728,6 +730,32 @@ int flame_hip_frontend_set_ref_grad(flame_hip_frontend* fe, float min_grad);
  * a handle without a device.  Errors: ARG (NULL fe, on outside {0, 1}); the setting then stays what it was.  Info keys "warp",
  * "warp_refused". */
 int flame_hip_frontend_set_warp(flame_hip_frontend* fe, int32_t on);
+
+/* ---- hand-over (opt-in): a feature belongs to the pose frame it was detected in, and when a new pose frame takes a ring slot that
+ * is in use every feature of the pose frame it overwrites dies before the frame is tracked.  A camera that hovers keeps those
+ * features in view, and the first pose frames hold nearly all of them: the eviction of one pose frame empties the graph
+ * (DESIGN.md 6).  With on = 1 a pose frame that takes a ring slot a in use (an EVICTING frame) runs in another order (DESIGN.md 5.3
+ * "Hand-over"; restated in tests/fe_carry_ref.py, which the GPU equals bit for bit); every other frame is what it was:
+ *   1. the image goes into the handle's extra image slot; ring slot a keeps the old pose frame's image, and its pose record is the
+ *      old pose frame's against the new pose; nothing is killed;
+ *   2. tracking, detection and compaction run as they are: the old pose frame's features are tracked against the new image, take
+ *      part in the cell competition and are emitted when they win their cell; new detections refer to ring slot a.  The frame's
+ *      output is what these stages produce;
+ *   3. behind them, every live slot of ring slot a whose status is not NEW is an old feature.  It is CARRIED iff its status is OK
+ *      or NO_PARALLAX, the frame emitted it (it won its cell), and with (px, py, idepth, var) its emitted record, ur =
+ *      (int)floorf(px + 0.5f), vr = (int)floorf(py + 0.5f), m = win_size / 2 + 1: m <= ur < W - m and max(m, y_lo) <= vr <
+ *      min(H - m, y_hi) (y_lo, y_hi: the letterbox band, 0 and H without one) -- a pixel where a detection could sit.  A carried
+ *      slot gets reference pixel (ur, vr) and prior (idepth, var), the emitted bits; its pose frame slot, dropout count, status,
+ *      k* and search record stay.  Every other old feature dies (its status and search record stay; its cell stays without a
+ *      feature until the next pose frame);
+ *   4. the image is copied into ring slot a on the handle's stream; the slot's id and pose become the new pose frame's.
+ * From the next frame on a carried feature is an ordinary feature of the new pose frame.  _prune and _set_poses are unchanged.
+ * NOT claimed: the anchor moves by up to half a pixel per axis and the prior is not corrected for the surface's slope over that
+ * distance; no variance is added at a hand-over.
+ * Takes effect with the next evicting frame and may change between any two frames (the feature state holds nothing of it).  Valid
+ * on a handle without a device.  Errors: ARG (NULL fe, on outside {0, 1}); the setting then stays what it was.  Info keys "carry",
+ * "carried", "carry_lost". */
+int flame_hip_frontend_set_carry(flame_hip_frontend* fe, int32_t on);
 
 /* Debug/test hook (no device needed; works on a handle created with device = -1): copies the
  * named host-side plan array ("v_o2i", "e_o2i", "grow", "ginc", "eij", "tiles", "t_vmap",

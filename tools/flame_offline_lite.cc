@@ -50,6 +50,10 @@
 // --warp-window (needs --gpu-frontend): Params::warp_matching_window -- the tracker samples the current image where the reference
 // window's pixels land under the pose change (flame_hip_frontend_set_warp): for cameras that roll or change their distance.  The
 // frame line ends with `fail_warp <n>`, the stat key num_fail_warp of the frame.
+// --carry-features (needs --gpu-frontend): Params::carry_features -- when a pose frame takes a slot of the pose-frame ring that is in
+// use, the features of the pose frame it evicts that the frame still emits move to the new pose frame instead of dying
+// (flame_hip_frontend_set_carry): for cameras that hover.  The frame line ends with `carried <n> carry_lost <n>`, the stat keys
+// num_carried / num_carry_lost of the frame.  --max-poseframes N (needs --gpu-frontend): the ring's size (1 ... 64, default 16).
 // --dump dir: frame_<id>.bin = {int32 V, T; float pos[2V], idepth_mu[V], idepth_var[V]; int32 tris[3T]; float idepth[V]}:
 // what went into the regulariser and what came out, for a bit-for-bit comparison with the oracle (tests).
 #include <cmath>
@@ -90,6 +94,7 @@ struct Lite {
   bool have_up = false;
   float up[3] = {0.f, -1.f, 0.f};
   int gates_error = 0;
+  int max_poseframes = 16;  // --max-poseframes: flame::GpuFrontEnd's pose-frame ring
 
   flame::FrontEnd frontEnd() {
     flame::FrontEnd fe;
@@ -118,7 +123,7 @@ struct Lite {
     Kinv(2, 0) = 0.f; Kinv(2, 1) = 0.f; Kinv(2, 2) = 1.f;
     sensor = std::make_shared<flame::Flame>(W, H, K, Kinv, params);
     if (gpu_frontend) {
-      gpu.reset(new flame::GpuFrontEnd(W, H, K, params));
+      gpu.reset(new flame::GpuFrontEnd(W, H, K, params, 4096, max_poseframes));
       if (raw_camera && !gpu->setCamera(W, H, 1, D)) std::fprintf(stderr, "--gpu-rectify: hip_error %d\n", gpu->lastError());
       if (gates && gpu->handle()) {  // (Params carried the band into the constructor; the up axis is the front end's own)
         gates_error = gpu->gates().letterbox || gpu->gates().height_gate ? gpu->lastError() : 0;
@@ -222,6 +227,9 @@ struct Lite {
     }
     if (params.warp_matching_window)  // (appended at the end: without the flag the line is what it was)
       std::printf(" fail_warp %d", st.stats().count("num_fail_warp") ? static_cast<int>(st.stats("num_fail_warp")) : -1);
+    if (params.carry_features)  // (appended at the end: without the flag the line is what it was)
+      std::printf(" carried %d carry_lost %d", st.stats().count("num_carried") ? static_cast<int>(st.stats("num_carried")) : -1,
+                  st.stats().count("num_carry_lost") ? static_cast<int>(st.stats("num_carry_lost")) : -1);
     std::printf("\n");
   }
 };
@@ -231,7 +239,7 @@ struct Lite {
 int main(int argc, char** argv) {
   std::vector<char*> args;
   Lite L;
-  bool gpu_rectify = false, bad_up = false, win_flag = false, rg_flag = false;
+  bool gpu_rectify = false, bad_up = false, win_flag = false, rg_flag = false, ring_flag = false;
   for (int k = 1; k < argc; ++k) {
     if (!std::strcmp(argv[k], "--dump") && k + 1 < argc) L.dump_dir = argv[++k];
     else if (!std::strcmp(argv[k], "--project-graph")) L.params.project_graph = true;  // warm-start every frame from the last mesh
@@ -242,6 +250,8 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[k], "--zero-mean")) L.params.zero_mean_matching = true;
     else if (!std::strcmp(argv[k], "--gain-invariant")) L.params.gain_invariant_matching = true;
     else if (!std::strcmp(argv[k], "--warp-window")) L.params.warp_matching_window = true;
+    else if (!std::strcmp(argv[k], "--carry-features")) L.params.carry_features = true;
+    else if (!std::strcmp(argv[k], "--max-poseframes") && k + 1 < argc) { L.max_poseframes = std::atoi(argv[++k]); ring_flag = true; }
     else if (!std::strcmp(argv[k], "--win-size") && k + 1 < argc) { L.params.zparams.win_size = std::atoi(argv[++k]); win_flag = true; }
     else if (!std::strcmp(argv[k], "--min-epipolar-grad") && k + 1 < argc) { L.params.min_epipolar_grad = static_cast<float>(std::atof(argv[++k])); rg_flag = true; }
     else if (!std::strcmp(argv[k], "--letterbox")) { L.params.do_letterbox = true; L.gates = true; }
@@ -256,7 +266,8 @@ int main(int argc, char** argv) {
   const bool asl = !args.empty() && !std::strcmp(args[0], "asl");
   if (!args.empty() && (!std::strcmp(args[0], "tum") || asl)) args.erase(args.begin());
   const bool bad_flags = (!L.debug_dir.empty() && !L.gpu_frontend) || (!L.dump_dir.empty() && L.gpu_frontend) ||
-                         ((L.gates || L.have_up || L.params.zero_mean_matching || L.params.gain_invariant_matching || L.params.warp_matching_window || win_flag || rg_flag) && !L.gpu_frontend) || bad_up;
+                         ((L.gates || L.have_up || L.params.zero_mean_matching || L.params.gain_invariant_matching || L.params.warp_matching_window || L.params.carry_features || win_flag || rg_flag || ring_flag) && !L.gpu_frontend) || bad_up ||
+                         (ring_flag && (L.max_poseframes < 1 || L.max_poseframes > 64));
   if (bad_flags || (asl && args.size() < 4) || (!asl && args.size() < 6)) {
     std::fprintf(stderr, "usage: %s [tum] index.txt frame fx fy cx cy [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-frontend [--debug-images dir]]\n       %s asl pose_dir rgb_dir depth_dir world_frame [iters] [--dump dir] [--project-graph] [--photo-error] [--gpu-rectify] [--gpu-frontend [--debug-images dir]]\n"
                  "  --gpu-frontend: features from the GPU tracker (not with --dump); --debug-images dir: detections_<id>.ppm / matches_<id>.ppm per frame (needs --gpu-frontend)\n"
@@ -264,6 +275,7 @@ int main(int argc, char** argv) {
                  "  --zero-mean (needs --gpu-frontend): match with the zero-mean SSD, which a grey offset between frames cannot move (auto-exposure cameras); --win-size N: the matching window (odd, <= 9)\n"
                  "  --gain-invariant (needs --gpu-frontend): match with the gain-invariant cost, which an exposure step between frames cannot move; overrides --zero-mean\n"
                  "  --warp-window (needs --gpu-frontend): sample the current image where the reference window lands under the pose change (cameras that roll or change their distance)\n"
+                 "  --carry-features (needs --gpu-frontend): features of a pose frame that the ring evicts move to the pose frame that takes its slot (cameras that hover); --max-poseframes N: the ring's size (1 ... 64, default 16)\n"
                  "  --min-epipolar-grad G (needs --gpu-frontend): do not search a feature whose reference window has a gradient below G along its epipolar line (0 = off)\n",
                  argv[0], argv[0]);
     return 2;

@@ -26,7 +26,14 @@ identity and the features are the same bits).
 --min-epipolar-grad G: the same pairs with the reference-patch gradient gate (GpuFrontEnd.set_ref_grad: the gated instantiation of
 k_fe_track -- 2 x 3 byte loads per lane and three wave sums in front of every search; a refused feature skips its search).
 
-    python tools/frontend_bench.py [--frames 100] [--warmup 10] [--gates] [--zero-mean] [--gain-invariant] [--warp] [--win-size 7] [--min-epipolar-grad 5] [--repeat 5]
+--carry: the device time of an EVICTING pose frame with the hand-over (GpuFrontEnd.set_carry) on against the same frame with it
+off.  The pairs alternate -- (pose frame a, tracking b), (pose frame b, tracking a) -- so that every pose frame sees the features of
+the pose frame it evicts `shift` pixels away: with the switch off they are killed and every cell detects again, as above; with it on
+they are searched against the new image once more (the work of a tracking frame inside the pose frame), k_fe_carry runs behind the
+compaction and the image is copied into the ring slot (W x H bytes, device to device).  Each of --repeat N runs is one off run and
+one on run; the medians of the runs' medians are reported side by side.
+
+    python tools/frontend_bench.py [--frames 100] [--warmup 10] [--gates] [--zero-mean] [--gain-invariant] [--warp] [--carry] [--win-size 7] [--min-epipolar-grad 5] [--repeat 5]
 """
 import argparse
 import json
@@ -51,7 +58,7 @@ def texture(h, w, seed=5, factor=8):
     return np.floor(up + 0.5).astype(np.uint8)
 
 
-def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=False, win_size=5, min_epipolar_grad=0.0, gain_invariant=False, warp=False):
+def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=False, win_size=5, min_epipolar_grad=0.0, gain_invariant=False, warp=False, carry=None):
     from flame_ros_amd.frontend import GpuFrontEnd, default_frontend_params
     K = np.array([525, 0, 319.5, 0, 525, 239.5, 0, 0, 1], np.float32)
     big = texture(H, W + shift)
@@ -62,7 +69,7 @@ def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=Fal
     p = default_frontend_params(win_size=win_size)
     t = {"poseframe": {"device": [], "host": []}, "tracking": {"device": [], "host": []}}
     with GpuFrontEnd(W, H, K, max_features=2048, max_poseframes=1) as fe:
-        live = ok = held = refused = fail_rg = 0
+        live = ok = held = refused = fail_rg = carried = carry_lost = 0
         if gates:
             fe.set_gates(letterbox=True, min_height=-0.15, max_height=0.15)
         if zero_mean:
@@ -73,9 +80,14 @@ def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=Fal
             fe.set_warp(True)
         if min_epipolar_grad > 0:
             fe.set_ref_grad(min_epipolar_grad)
+        if carry is not None:
+            fe.set_carry(carry)
         for i in range(warmup + frames):
-            for kind, img, T, pf in (("poseframe", a, Ta, True), ("tracking", b, Tb, False)):
+            swap = carry is not None and i % 2 == 1  # --carry: the pairs alternate, every pose frame evicts one `shift` pixels away
+            for kind, img, T, pf in (("poseframe", b if swap else a, Tb if swap else Ta, True), ("tracking", a if swap else b, Ta if swap else Tb, False)):
                 fe.track(p, img, 2 * i + (not pf), T, pf)
+                if pf and carry:
+                    carried, carry_lost = fe.info("carried"), fe.info("carry_lost")
                 if i >= warmup:
                     t[kind]["device"].append(fe.info("track_device_us"))
                     t[kind]["host"].append(fe.info("track_us"))
@@ -91,6 +103,8 @@ def run(frames=100, warmup=10, W=640, H=480, shift=6, gates=False, zero_mean=Fal
         res.update(gain_invariant=1)
     if warp:
         res.update(warp=1)
+    if carry is not None:
+        res.update(carry=int(carry), carried=carried, carry_lost=carry_lost)
     if min_epipolar_grad > 0:
         res.update(min_epipolar_grad=min_epipolar_grad, fail_ref_grad=fail_rg)
     if win_size != 5:
@@ -109,11 +123,26 @@ if __name__ == "__main__":
     ap.add_argument("--zero-mean", action="store_true")
     ap.add_argument("--gain-invariant", action="store_true")
     ap.add_argument("--warp", action="store_true")
+    ap.add_argument("--carry", action="store_true")
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--win-size", type=int, default=5)
     ap.add_argument("--min-epipolar-grad", type=float, default=0.0)
     a = ap.parse_args()
-    runs = [run(max(a.frames, 50), a.warmup, gates=a.gates, zero_mean=a.zero_mean, win_size=a.win_size, min_epipolar_grad=a.min_epipolar_grad, gain_invariant=a.gain_invariant, warp=a.warp) for _ in range(max(a.repeat, 1))]
+    kw = dict(gates=a.gates, zero_mean=a.zero_mean, win_size=a.win_size, min_epipolar_grad=a.min_epipolar_grad, gain_invariant=a.gain_invariant, warp=a.warp)
+    if a.carry:  # off and on alternate; every run is a handle of its own
+        off, on = [], []
+        for _ in range(max(a.repeat, 1)):
+            off.append(run(max(a.frames, 50), a.warmup, carry=False, **kw))
+            on.append(run(max(a.frames, 50), a.warmup, carry=True, **kw))
+        res = on[-1]
+        for name, rs in (("off", off), ("on", on)):
+            for kind in ("poseframe", "tracking"):
+                t = [r[kind + "_device_us"] for r in rs]
+                res["%s_device_us_carry_%s" % (kind, name)] = float(np.median(t))
+                res["%s_device_us_carry_%s_runs" % (kind, name)] = t
+        print(json.dumps({"frontend_track": res}))
+        sys.exit(0)
+    runs = [run(max(a.frames, 50), a.warmup, **kw) for _ in range(max(a.repeat, 1))]
     res = runs[-1]
     if a.repeat > 1:
         t = [r["tracking_device_us"] for r in runs]
