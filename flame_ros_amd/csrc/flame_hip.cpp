@@ -6,9 +6,9 @@
 // (reference call sites src/flame_offline_tum.cc:578-579, results out :628-635, stats
 // src/utils.cc:131-136).  No CPU fallback exists here: without a device every compute entry
 // point returns FLAME_HIP_ERR_NODEVICE.
-#include "../../include/flame_hip.h"
-
-#include <hip/hip_runtime.h>
+//
+// The handle itself is defined in graph_handle.h; solves by ONE launch of resident tiles, and everything that recovers
+// them, are the handle's member g->res (resident.h / resident.cpp) -- the driver here only asks it.
 #include <roctracer/roctx.h>
 
 #include <atomic>
@@ -16,34 +16,20 @@
 #include <climits>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <new>
 #include <string>
-#include <unordered_map>
-#include <mutex>
-#include <vector>
 
-#include "delaunay_dev.h"
 #include "evaluate.h"
-#include "kernels.h"
-#include "plan.h"
-#include "plan_dev.h"
+#include "graph_handle.h"
 #include "predict.h"
-#include "sync.h"
 
 using namespace flamehip;
-
-#define HIPCHK(expr)                                             \
-  do {                                                           \
-    hipError_t e__ = (expr);                                     \
-    if (e__ != hipSuccess) return FLAME_HIP_ERR_HIP - (int)e__;  \
-  } while (0)
 
 // Fault injection for the tests, compiled ONLY into flame_ros_amd/libflame_hip_hooks.so (-DFLAME_HIP_TEST_HOOKS=1, built by
 // flame_ros_amd/build.py beside the product library; tests ask for it by name, tests/util.py hooks_env()).  The product
 // library reads no environment variable and has no such switch.  flame_hip_test_hook(key, value), process-wide:
-//   "persist_fail" 1      every launch of resident tiles counts as having given up (the recovery paths)
+//   "persist_fail" 1      every launch of resident tiles counts as having given up, wherever its error word is looked at
+//                         (the recovery paths; read by resident.cpp through test_persist_fail())
 //   "fill_alloc"   0..255 new device allocations are filled with that byte (stale-read detection), -1 off
 //   "persist_stall_us" n  tile 0 is REALLY late by n us behind its first hand-off (needs kernels.hip built with
 //                         -DFLAME_PERSIST_STALL_HOOK=1: tools/exp/build_variant.sh)
@@ -69,6 +55,8 @@ extern "C" int flame_hip_test_hook(const char* key, int32_t value) {
 #define TEST_HOOK(name, off) (off)
 #endif
 int flamehip::test_alloc_fill() { return TEST_HOOK(fill_alloc, -1); }
+bool flamehip::test_persist_fail() { return TEST_HOOK(persist_fail, 0) != 0; }
+int flamehip::test_persist_stall_us() { return TEST_HOOK(persist_stall_us, 0); }
 
 namespace {
 
@@ -78,101 +66,6 @@ struct RoctxRange {
   ~RoctxRange() { roctxRangePop(); }
 };
 
-struct GraphExecEntry {
-  int32_t iters;
-  int cur;
-  SolveParams p;
-  hipGraphExec_t exec;
-  int launches;
-};
-
-// Device buffers are owned by the handle and keep their capacity across uploads (a frame stream
-// re-uploads a similar graph every frame: no hipMalloc/hipFree after the first few frames).
-// `caps` maps the address of the pointer member to its capacity in bytes.
-typedef std::unordered_map<void*, size_t> CapMap;
-
-template <class T>
-int dev_alloc(CapMap& caps, T** p, size_t n) {
-  n += 1;  // one pad element: kernels clamp indices of empty lists to element 0
-  const size_t bytes = n * sizeof(T);
-  auto it = caps.find((void*)p);
-  if (*p && it != caps.end() && it->second >= bytes) return 0;
-  if (*p && it != caps.end()) (void)hipFree(*p);  // (no entry: the pointer lives inside the upload arena)
-  *p = nullptr;
-  const size_t want = bytes + bytes / 4;  // slack for the next, slightly larger frame
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), want);
-  if (e == hipErrorOutOfMemory) return FLAME_HIP_ERR_ALLOC;
-  if (e != hipSuccess) return FLAME_HIP_ERR_HIP - (int)e;
-  const int fill = flamehip::test_alloc_fill();  // (-1 in the product library)
-  if (fill >= 0) (void)hipMemset(*p, fill, want);
-  caps[(void*)p] = want;
-  return 0;
-}
-
-// ... in UNCACHED device memory (hipDeviceMallocUncached: no L2 holds it, so stores and loads of different XCDs meet in
-// memory while a kernel runs -- the hand-off copies of the resident tiles, kernels.hip PersistArgs).  Uncached blocks
-// are never handed back to the runtime: on this stack (ROCm 7.2) a later ordinary hipMalloc that recycles such a
-// block misbehaves (tools/exp/fault_repro.py: the plan builder's kernels fault on it), so freed blocks wait in a
-// process-wide pool, per device, for the next uncached request (bounded by the largest graph the process has seen).
-struct UncachedPool {
-  std::mutex m;
-  struct Block { void* p; size_t bytes; int device; };
-  std::vector<Block> free_blocks;
-  void* take(int device, size_t bytes, size_t* got) {
-    std::lock_guard<std::mutex> lk(m);
-    size_t best = free_blocks.size();
-    for (size_t i = 0; i < free_blocks.size(); ++i)
-      if (free_blocks[i].device == device && free_blocks[i].bytes >= bytes &&
-          (best == free_blocks.size() || free_blocks[i].bytes < free_blocks[best].bytes))
-        best = i;
-    if (best == free_blocks.size()) return nullptr;
-    void* p = free_blocks[best].p;
-    *got = free_blocks[best].bytes;
-    free_blocks.erase(free_blocks.begin() + (long)best);
-    return p;
-  }
-  void give(int device, void* p, size_t bytes) {
-    std::lock_guard<std::mutex> lk(m);
-    free_blocks.push_back({p, bytes, device});
-  }
-};
-static UncachedPool& uncached_pool() {
-  static UncachedPool* pool = new UncachedPool();  // (never destroyed: handles may outlive static destruction order)
-  return *pool;
-}
-// (the blocks are NOT registered in the handle's CapMap: free_device() must not hipFree them; *cap = bytes of *p)
-template <class T>
-int dev_alloc_uncached(int device, T** p, size_t* cap, size_t n, bool* fresh) {
-  n += 1;
-  const size_t bytes = n * sizeof(T);
-  *fresh = false;
-  if (*p && *cap >= bytes) return 0;
-  if (*p) uncached_pool().give(device, *p, *cap);
-  *p = nullptr; *cap = 0;
-  *fresh = true;  // (contents unknown: the caller zeroes it)
-  size_t got = 0;
-  if (void* q = uncached_pool().take(device, bytes, &got)) {
-    *p = static_cast<T*>(q); *cap = got;
-    return 0;
-  }
-  const size_t want = bytes + bytes / 4;
-  hipError_t e = hipExtMallocWithFlags(reinterpret_cast<void**>(p), want, hipDeviceMallocUncached);
-  if (e == hipErrorOutOfMemory) return FLAME_HIP_ERR_ALLOC;
-  if (e != hipSuccess) return FLAME_HIP_ERR_HIP - (int)e;
-  *cap = want;
-  return 0;
-}
-
-// All copies go through the handle's own non-blocking stream (hipMemcpyAsync + stream sync),
-// never the legacy stream: a legacy-stream copy in one host thread collides with a stream capture
-// running in another thread (hipErrorStreamCaptureImplicit), and distinct handles must be usable
-// from distinct threads.
-inline hipError_t memcpy_sync(hipStream_t s, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-  hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, s);
-  if (e != hipSuccess) return e;
-  return hipStreamSynchronize(s);
-}
-
 template <class T>
 int h2d(hipStream_t s, T* dst, const std::vector<T>& src) {
   if (src.empty()) return 0;
@@ -180,42 +73,10 @@ int h2d(hipStream_t s, T* dst, const std::vector<T>& src) {
   return 0;
 }
 
-// Asynchronous variant for the upload path: the source vectors outlive the call (plan members or
-// locals of a function that synchronises the stream before it returns), so a whole upload pays one
-// stream synchronisation instead of one per array.
-// Page-locked staging area of a handle: host arrays are copied into it once and leave through
-// truly asynchronous DMAs (a hipMemcpyAsync from pageable memory is staged and waited for by the
-// runtime, call by call -- ~10 us each, the larger part of a small frame's upload).
+constexpr int kMapMinTiles = 6;  // partitions of at least this many tiles leave a tile map for the next frame (partition reuse)
 // frame_results: outputs up to this size are written to host memory by the kernels themselves (measured on
 // the facade stream, direct vs one copy: 1.2 k -14 us, 5 k -10 us, 10 k (185 KB) -15 us, 50 k (925 KB) +65 us)
-constexpr int kPollDelayDefault = 2;  // x 256 clocks.  r05, address-sorted poll: a pass is short enough to sample memory before the neighbours' stores have landed (passes per round 1.35 at 0, 1.10 at 2, 1.01 at 3; 50 k 1.316 / 1.319 / 1.304 / 1.303 / 1.357 us per iteration at 0 / 1 / 2 / 3 / 4, profiles/r05_sorted_poll_delay.txt; swept again in r06 behind the one-block poll: 1.313 / 1.334 / 1.309 / 1.329 / 1.350); option "poll_delay" overrides
-constexpr int kMapMinTiles = 6;  // partitions of at least this many tiles leave a tile map for the next frame (partition reuse)
 constexpr size_t kDirectOutBytes = 256 * 1024;
-
-struct PinnedArena {
-  char* base = nullptr;
-  size_t cap = 0, used = 0;
-  // room for `bytes` more (only ever grows between uploads: call with nothing in flight)
-  hipError_t reserve(size_t bytes) {
-    used = 0;
-    if (bytes <= cap) return hipSuccess;
-    if (base) (void)hipHostFree(base);
-    base = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 2 + 4096;
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&base), want, hipHostMallocDefault);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void* put(const void* src, size_t bytes) {
-    used = (used + 63) & ~(size_t)63;
-    if (used + bytes > cap) return nullptr;
-    void* p = base + used;
-    std::memcpy(p, src, bytes);
-    used += bytes;
-    return p;
-  }
-  void release() { if (base) (void)hipHostFree(base); base = nullptr; cap = used = 0; }
-};
 
 // H2D of a host vector through the arena (falls back to the pageable source if it does not fit)
 template <class T>
@@ -257,6 +118,9 @@ struct D2HBatch {
   }
 };
 
+// Asynchronous variant for the upload path: the source vectors outlive the call (plan members or
+// locals of a function that synchronises the stream before it returns), so a whole upload pays one
+// stream synchronisation instead of one per array.
 template <class T>
 int h2d_async(hipStream_t s, T* dst, const std::vector<T>& src) {
   if (src.empty()) return 0;
@@ -272,257 +136,45 @@ bool all_finite(const float* p, size_t n) {
 
 }  // namespace
 
-struct flame_hip_graph {
-  int device = -1;
-  int32_t V = 0, E = 0, T = 0;
-  bool uploaded = false;
-  PlanOptions opt;
-  int num_cus = 0;
-  int use_graph = 1;
-  Plan plan;
-  SyncOut sync;          // inputs derived by flame_hip_graph_sync (kept for flame_hip_graph_edges)
-  bool synced = false;   // the current graph came from flame_hip_graph_sync
-  int path = 0;  // resolved path after upload
+// The arguments every tile launch of a solve shares (the buffers and the iteration count are the launch's own)
+TileArgs flamehip::tile_args(const flame_hip_graph* g, const SolveParams& sp) {
+  const Plan& P = g->plan;
+  TileArgs a;
+  a.tiles = g->tiles; a.t_vmap = g->t_vmap; a.t_emap = g->t_emap; a.t_eij = g->t_eij;
+  a.t_ew = g->t_ew; a.t_srow = g->t_srow; a.p = sp; a.ntiles = (int32_t)P.tiles.size();
+  a.prof = g->prof;
+  a.slot12 = P.tile_slot12 ? 1 : 0;
+  a.fat = P.tile_fat ? 1 : 0;
+  return a;
+}
 
-  hipStream_t stream = nullptr;
-  hipStream_t stream_in = nullptr;  // input staging (H2D of a frame overlaps the partition kernels)
-  DelaunayScratch dt;               // flame_hip_delaunay: arenas kept between frames
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_in = nullptr;
-  hipEvent_t ev_state = nullptr;  // last state-writing work on `stream` (upload, scale, filter, results)
-  bool state_pending = false;     // ev_state was recorded since the last full synchronisation
-  float state_scale = 1.0f;       // factor applied to the resident state since its upload (rescale_data epilogue)
-  bool timed = false;
-  int last_launches = 0;
-
-  float4* A[2] = {nullptr, nullptr};
-  float4* B[2] = {nullptr, nullptr};
-  float4* q[2] = {nullptr, nullptr};
-  int cur = 0;
-  int2* eij = nullptr;
-  float4* ew = nullptr;
-  int32_t* grow = nullptr;
-  int32_t* ginc = nullptr;
-  float2* pos = nullptr;
-  // tiles
-  TileDesc* tiles = nullptr;
-  int32_t* t_vmap = nullptr;
-  int32_t* t_emap = nullptr;
-  uint2* t_eij = nullptr;
-  float4* t_ew = nullptr;
-  uint32_t* t_srow = nullptr;
-  // triangles
-  int32_t* tris = nullptr;
-  int32_t* trow = nullptr;
-  int32_t* tinc = nullptr;
-  float4* tri_normals = nullptr;
-  float4* vtx_normals = nullptr;
-  uint8_t* tri_valid = nullptr;
-  // dense maps (row f2), allocated on first use for the requested image size
-  int64_t map_pixels = 0;
-  uint32_t* map_owner = nullptr;
-  float* map_idm = nullptr;
-  float* map_dm = nullptr;
-  float* map_cloud = nullptr;
-  uint32_t* map_cov = nullptr;   // per-block covered-pixel counts of the last raster (stat key coverage)
-  char* fr_dev = nullptr;        // output arena of flame_hip_frame_results (one D2H per frame)
-  uint32_t* dbg_key = nullptr;   // debug images: winning-primitive key map, BGR8 output, staged features
-  uint8_t* dbg_bgr = nullptr;
-  float* dbg_feat = nullptr;
-  // which raster the map buffers hold: the solver state it was made from (state_serial), the
-  // filter parameters, filtered or not -- dense maps, coverage and the debug images share it
-  uint64_t state_serial = 1, raster_serial = 0;
-  int raster_filtered = -1;
-  flame_hip_tri_params raster_tp;
-  float raster_kinv[9];
-  // prediction stage (flame_hip_predict, predict.h): scratch sized like the dense raster's and kept across frames
-  bool tri_stage_run = false;    // a triangle stage has written tri_valid since the last upload
-  bool is_batch = false;         // the handle holds a batch of graphs (flame_hip_graph_upload_batch)
-  int64_t pg_pixels = 0;         // W x H of the key map the last flame_hip_predict made (0 = none)
-  unsigned long long* pg_key = nullptr;
-  float4* pg_proj = nullptr;
-  float2* pg_pix = nullptr;
-  float* pg_pred = nullptr;
-  float* pg_map = nullptr;
-  hipEvent_t pg_ev0 = nullptr, pg_ev1 = nullptr;
-  double predict_us = 0.0, predict_device_us = 0.0;
-  // evaluate stage (flame_hip_photo_reference / _photo_error / _truth_stats, evaluate.h): two dense images -- ev_img[ev_cmp]
-  // the comparison frame, the other one the current image of the last photo_error call (promoted without a second upload) --,
-  // the uploaded map / depth, the error map, the words and the partials; kept across frames, re-allocated only when W x H grows
-  uint8_t* ev_img[2] = {nullptr, nullptr};
-  int ev_cmp = 0;
-  bool ev_has_ref = false, ev_has_cur = false;
-  int32_t ev_ref_W = 0, ev_ref_H = 0, ev_cur_W = 0, ev_cur_H = 0;
-  double ev_ref_pose[12] = {0.0}, ev_cur_pose[12] = {0.0};
-  float* ev_map = nullptr;
-  float* ev_depth = nullptr;
-  float* ev_err = nullptr;
-  unsigned long long* ev_words = nullptr;
-  double* ev_partial = nullptr;
-  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
-  double photo_us = 0.0, photo_device_us = 0.0, truth_us = 0.0;
-  // graph filter scratch (row a9)
-  float* filter_tmp = nullptr;
-  // mesh output (row f1)
-  float4* mesh_pts = nullptr;
-  // permutations on the device (results leave in the caller's order without a host pass)
-  int32_t* v_i2o_dev = nullptr;
-  int32_t* v_o2i_dev = nullptr;
-  int32_t* e_i2o_dev = nullptr;
-  int32_t* e_o2i_dev = nullptr;
-  float* dl_v = nullptr;  // download staging: 3V floats
-  float* dl_q = nullptr;  // 3E floats
-  float* dl_n = nullptr;  // 3V floats (vertex normals of flame_hip_frame_results)
-  // device plan builder (row f3) and the staged inputs it reads (caller's order)
-  int plan_device = 1;
-  int plan_reuse = 1;          // frame streams: partition from the previous frame's tile map
-  int plan_mini = 1;           // option "plan_mini": small frames of a graph sync planned by one launch (k_mini_plan)
-  bool plan_mini_used = false; // ... the current plan was
-  // option "persist" (default 1): graphs of 2 .. min(kPersistMaxTiles, CUs) halo tiles are solved by ONE launch of
-  // RESIDENT tiles (kernels.hip k_tile_persist: round-tagged hand-offs through uncached memory instead of a kernel
-  // boundary per `depth` iterations); 0: launches
-  bool persist = true, persist_used = false;
-  float4 *snapA = nullptr, *snapB = nullptr, *snapq = nullptr;  // flame_hip_state_snapshot / _rollback
-  bool snap_valid = false;
-  int64_t persist_launches = 0;     // launches of resident tiles so far (info "persist_launches")
-  float persist_round_us = 0.f;     // device time of a round of the last resident solve that was looked at (0 = none yet)
-  int32_t persist_round_V = 0;      // ... and the size of the graph it was measured on
-  int32_t last_rounds = 0;          // rounds of the last resident launch
-  int32_t persist_timeout_us = 0;   // what the last resident launch was given (info "persist_timeout_us")
-  int32_t snap_V = 0, snap_E = 0;
-  PersistBufs xp;                   // hand-off buffers (uncached, from the process-wide pool: NOT in caps) + dev-aid words
-  size_t xp_cap[6] = {0, 0, 0, 0, 0, 0};
-  // r06, option "one_xcd" (default 1): a graph of up to 32 resident tiles keeps them on ONE XCD -- the launch has 8 x ntiles
-  // workgroups of which every 8th carries a tile -- and hands over through ORDINARY memory, i.e. that XCD's L2 (0.5 us per
-  // load instead of 0.9 through uncached memory: 1.2 k vertices 0.89 -> 0.81 us per iteration).  Which XCD a workgroup lands on
-  // is the dispatcher's habit, not a guarantee: tiles on different XCDs would never see each other's tags, time out, and the
-  // solve is repeated by launches like any give-up -- after which the device's lease never tries the mode again.
-  bool one_xcd_opt = true, one_xcd_used = false;
-  float4* cA[2] = {nullptr, nullptr};  // the hand-off copies in ordinary memory
-  float4* cB[2] = {nullptr, nullptr};
-  float4* cq[2] = {nullptr, nullptr};
-  void* c_zeroed[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // the allocations that have been zeroed (tag 0 is never a
-  size_t c_zeroed_cap[6] = {0, 0, 0, 0, 0, 0};                                 // round's): address AND capacity, i.e. no reallocation since
-  int poll_delay_opt = -1;          // option "poll_delay" (-1 = automatic)
-  int persist_timeout_opt = 0;      // option "persist_timeout_us" (0 = automatic)
-  bool need_marks = true;           // option "need_marks"
-  int persist_prof_want = 0, persist_prof_set = 0;  // option "persist_prof": tile + 1 that records its round split (0 = none)
-  bool persist_unchecked = false;   // a resident launch is in flight / finished and nobody has looked at persist_err yet
-  int persist_unchecked_n = 0;      // ... how many of them (the error word does not say WHICH launch gave up: only when it
-                                    // can only have been the last solve is that solve repeated)
-  bool persist_skip_once = false;   // the next enqueue goes by launches (the repeat of a solve that gave up)
-  int last_src = 0;                 // the buffer the last solve started from
-  int32_t* persist_err = nullptr;   // page-locked: raised by a launch whose wait timed out
-  int32_t persist_base = 0;         // the hand-off tags used so far (they only grow)
-  SolveParams last_sp{};            // the last solve (a persistent launch that gave up is repeated by launches)
-  int32_t last_iters = 0;
-  hipStream_t last_stream = nullptr;
-  bool init_have_x0 = false;        // the device-built plan's initial state came with an x0 array
-  int persist_recovered = 0;        // how many solves were repeated that way (flame_hip_get_info)
-  // the last give-up of this handle, for whoever has to find out why (info "persist_gave_up_tile" / _round / _front_round /
-  // _not_started / _rounds / _tiles / _one_xcd / _timeout_us, persist_note_give_up()): the tile that had handed over the fewest
-  // rounds and how many, the most any tile had, the tiles that had handed over none, the launch's rounds
-  struct GiveUp { int32_t tile = -1, round = -1, front_round = 0, not_started = 0, rounds = 0, tiles = 0, one_xcd = 0, timeout_us = 0; } give_up;
-  int32_t give_up_base = 0;         // persist_base of the last resident launch (its tags are give_up_base + 1 ..)
-  uint64_t solve_serial = 0;        // state_serial right behind the last solve: later state-writing calls move on from it
-  // r05: SEVERAL solves queued behind each other without a synchronising call are repeatable too (a bench window, a caller
-  // that pipelines solves): every solve from the first unchecked resident one on is logged, and when a second one is queued
-  // the source buffers of the first -- which it would overwrite -- are copied aside first (device to device, once per
-  // synchronising call).  A give-up then restores that state and repeats the whole queue by launches.
-  struct QueuedSolve { SolveParams sp; int32_t iters; };
-  std::vector<QueuedSolve> queued;  // since the last look, the first unchecked resident solve first
-  int queued_src = 0;               // the buffer that solve started from
-  uint64_t queued_serial = 0;       // state_serial in front of it
-  float4 *qsnapA = nullptr, *qsnapB = nullptr, *qsnapq = nullptr;
-  bool qsnap_valid = false;
-  int stream_depth = 0;        // option "stream_depth": halo depth of small graphs (<= 64 tiles) instead of the
-                               // auto depth 8, which is tuned for a RESIDENT graph (fewest launches); a graph
-                               // that is solved once pays for its plan, and that is cheapest at depth 4-5
-  int tile_imbalance_pct = 100; // info "tile_imbalance_pct": 100 x max / mean of the tiles' cost (e_loc + 2 n_ext)
-  int single_cap = 1 << 30;    // an isolated tile did not fit a graph of this many vertices + 1 on this handle
-  bool plan_reused = false;    // the current plan's partition came from the map
-  int reuse_tile_own_opt = 0;  // the "tile_own" option the map was made with
-  int reuse_backoff = 0, reuse_skip = 0;  // frames to sit out after a rejected reuse (doubles, <= 16)
-  // graph sync without waiting for the edge count: E is predicted (V + T + euler_off, -1 for a
-  // triangulated disk) and checked at the plan builder's first synchronisation
-  bool spec_edges = false;     // the current upload_device_plan() runs on a predicted count
-  int32_t true_edges = 0;      // ... and this is what the device counted when the prediction failed
-  int32_t euler_off = -1;      // E - V - T of the last frame
-  int euler_skip = 0, euler_backoff = 0;
-  DevPlanner planner;
-  float2* in_pos = nullptr;
-  int2* in_edges = nullptr;
-  float* in_alpha = nullptr;
-  float* in_beta = nullptr;
-  float* in_z = nullptr;
-  float* in_wgt = nullptr;
-  float* in_x0 = nullptr;
-  int32_t* in_tris = nullptr;
-  float* in_mu = nullptr;    // graph sync on the device: measured idepths, variances, predictions
-  float* in_var = nullptr;
-  float* in_pred = nullptr;
-  bool sync_on_device = false;  // the derived edge list lives in in_edges (sync.edges is stale)
-  bool beta_is_alpha = false;   // staged graph sync: beta = alpha, one buffer
-  int32_t* dflags = nullptr;
-  bool host_perms = true;  // plan.v_i2o / v_o2i / e_i2o / e_o2i / tris are valid on the host
-  // costs
-  double* partials = nullptr;
-  uint8_t* cost_mask = nullptr;  // flame_hip_costs_masked: V vertex flags then E edge flags, internal order
-  // halo exchange lists (internal ids), see flame_hip_halo_register
-  int32_t n_send_v = 0, n_send_e = 0, n_recv_v = 0, n_recv_e = 0;
-  int32_t* halo_send_v = nullptr;
-  int32_t* halo_send_e = nullptr;
-  int32_t* halo_recv_v = nullptr;
-  int32_t* halo_recv_e = nullptr;
-  // debug timeline of the tile kernel
-  int profile = 0;
-  unsigned long long* prof = nullptr;
-
-  std::vector<GraphExecEntry> execs;
-  CapMap caps;
-  int solves_since_upload = 0;
-  PinnedArena pin;             // page-locked staging of the host arrays of an upload
-  PinnedArena pin_in;          // ... of the inputs of a small graph sync (one DMA; k_mini_plan reads the device copy)
-  char* in_stage = nullptr;
-  PinnedArena pout;            // page-locked landing area of the results (frame_results, download)
-  char* harena = nullptr;      // device arena the host-built plan of the current upload lives in
-  bool lanes_applied = false;  // lane_order = 1: the conflict-avoiding lane order is in the device arrays
-  bool poll_valid = false;     // the resident tiles' poll lists (xp.poll_*) belong to the current tile arrays
-  bool poll_sorted = false;    // ... and are the address-sorted ones (from a plan's second solve on)
-
-  void drop_execs() {
-    for (auto& e : execs) (void)hipGraphExecDestroy(e.exec);
-    execs.clear();
-  }
-
-  void free_device() {
-    if (device < 0) return;
-    (void)hipSetDevice(device);
-    drop_execs();
-    // every device buffer of the handle is registered in `caps` (key = address of the member)
-    for (auto& kv : caps) {
-      void** pp = reinterpret_cast<void**>(kv.first);
-      if (*pp) (void)hipFree(*pp);
-      *pp = nullptr;
+int flamehip::enqueue_by_launches(flame_hip_graph* g, const SolveParams& sp, int32_t num_iters, hipStream_t s, int cur,
+                                  int* cur_out, int* launches) {
+  const Plan& P = g->plan;
+  *launches = 0;
+  if (g->path == FLAME_HIP_PATH_TILE) {
+    TileArgs a = tile_args(g, sp);
+    const int per = P.tile_depth > 0 ? P.tile_depth : num_iters;
+    for (int32_t done = 0; done < num_iters;) {
+      const int32_t n = std::min<int32_t>(per, num_iters - done);
+      a.A_src = g->A[cur]; a.B_src = g->B[cur]; a.q_src = g->q[cur];
+      a.A_dst = g->A[cur ^ 1]; a.B_dst = g->B[cur ^ 1]; a.q_dst = g->q[cur ^ 1];
+      a.iters = n;
+      HIPCHK(launch_tile(s, P.tile_threads, P.tile_ept, P.tile_vpt, (size_t)P.tile_lds_bytes, a));
+      cur ^= 1;
+      done += n;
+      ++*launches;
     }
-    caps.clear();
-    for (int b = 0; b < 2; ++b) {  // (uncached blocks go back to the pool, never to the runtime)
-      float4** pp[3] = {&xp.hA[b], &xp.hB[b], &xp.hq[b]};
-      for (int k = 0; k < 3; ++k) {
-        if (*pp[k]) uncached_pool().give(device, *pp[k], xp_cap[3 * b + k]);
-        *pp[k] = nullptr; xp_cap[3 * b + k] = 0;
-      }
+  } else {
+    for (int32_t it = 0; it < num_iters; ++it) {
+      HIPCHK(launch_dual(s, g->E, g->eij, g->ew, g->B[cur], g->q[cur], sp.sigma));
+      HIPCHK(launch_primal(s, g->V, g->grow, g->ginc, g->ew, g->q[cur], g->A[cur], g->B[cur], sp));
+      *launches += 2;
     }
-    xp.prof = nullptr;  // (was in caps)
-    xp.poll_v = nullptr; xp.poll_e = nullptr; xp.poll_ne = nullptr;
-    xp.need_v = nullptr; xp.need_e = nullptr; xp.need_valid = false;
-    pin.release();
-    pin_in.release();
-    pout.release();
-    map_pixels = 0;
-    ev_has_ref = ev_has_cur = false;
-    n_send_v = n_send_e = n_recv_v = n_recv_e = 0;
   }
-};
+  *cur_out = cur;
+  return 0;
+}
 
 extern "C" {
 
@@ -577,22 +229,16 @@ int flame_hip_graph_create(flame_hip_graph** out, int device, int32_t V, int32_t
   return 0;
 }
 
-static void persist_lease_drop(flame_hip_graph* g, bool gave_up);
-static int persist_gave_up_count(int device);
-static int persist_backoff(int device);
-static bool one_xcd_allowed(int device);
-
 void flame_hip_graph_destroy(flame_hip_graph* g) {
   if (!g) return;
   if (g->device >= 0) {
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     if (g->timed) (void)hipEventSynchronize(g->ev1);
-    persist_lease_drop(g, false);
+    g->res.release(g);
     (void)g->planner.wait_maps();
     g->free_device();
     g->dt.release();
-    if (g->persist_err) (void)hipHostFree(g->persist_err);
     if (g->ev0) (void)hipEventDestroy(g->ev0);
     if (g->ev1) (void)hipEventDestroy(g->ev1);
     if (g->ev_in) (void)hipEventDestroy(g->ev_in);
@@ -615,56 +261,6 @@ static hipError_t wait_last_solve(flame_hip_graph* g) {
   return hipEventSynchronize(g->ev1);
 }
 
-// A launch of resident tiles gave up: say how far its tiles got (cold path, nothing in the kernel -- a per-tile record written at
-// the time-out cost every size 3-5 % through the poll loop's registers and code layout, profiles/r06_giveup_record_ab.txt).
-// The x_bar hand-off copies of both parities still hold what the LAST launch's tiles stored: a tile's highest tag above the
-// launch's base is the last round it handed over.  The tile with the lowest one is the late one (0 rounds: it never started) or,
-// when the late one caught up after its neighbours had stopped, stood next to it.  analyse = false: the plan is no longer the
-// launch's (a new upload), only the launch's own numbers are kept.
-static void persist_note_give_up(flame_hip_graph* g, bool analyse = true) {
-  flame_hip_graph::GiveUp u;
-  u.tiles = (int32_t)g->plan.tiles.size();
-  u.one_xcd = g->one_xcd_used ? 1 : 0;
-  u.timeout_us = g->persist_timeout_us;
-  u.rounds = g->last_rounds;
-  const int32_t V = g->V, base = g->give_up_base;
-  float4* const* hB = g->one_xcd_used ? g->cB : g->xp.hB;
-  if (analyse && V > 0 && hB[0] && hB[1] && g->persist_used && *g->persist_err == 1) {  // (a forced failure of the hooks library: nothing to look at)
-    std::vector<float4> e0((size_t)V), e1((size_t)V);
-    if (hipMemcpy(e0.data(), hB[0], sizeof(float4) * (size_t)V, hipMemcpyDeviceToHost) == hipSuccess &&
-        hipMemcpy(e1.data(), hB[1], sizeof(float4) * (size_t)V, hipMemcpyDeviceToHost) == hipSuccess) {
-      for (int t = 0; t < u.tiles; ++t) {
-        const TileDesc& T = g->plan.tiles[t];
-        int32_t last = 0;
-        for (int32_t v = T.vstart; v < T.vstart + T.n_own && v < V; ++v)
-          for (const float4* e : {&e0[(size_t)v], &e1[(size_t)v]}) {
-            int32_t tag;
-            std::memcpy(&tag, &e->w, sizeof(tag));
-            if (tag > base && tag - base <= u.rounds) last = std::max(last, tag - base);
-          }
-        if (last == 0) ++u.not_started;
-        if (u.tile < 0 || last < u.round) { u.tile = t; u.round = last; }
-        u.front_round = std::max(u.front_round, last);
-      }
-    } else (void)hipGetLastError();
-  }
-  g->give_up = u;
-}
-
-// A new upload throws the state of the solves before it away: whether one of their resident launches gave up no longer
-// matters for the results -- only for the lease and the back-off.  (Called behind the upload's own wait for those solves.)
-static void persist_discard(flame_hip_graph* g) {
-  g->queued.clear(); g->qsnap_valid = false;
-  if (!g->persist_unchecked) return;
-  g->persist_unchecked = false;
-  g->persist_unchecked_n = 0;
-  if (g->persist_err && *g->persist_err != 0) {
-    persist_note_give_up(g, false);
-    *g->persist_err = 0;
-    persist_lease_drop(g, true);
-  }
-}
-
 // State-writing work enqueued on the handle's own stream (upload, un-scaling, filters) is marked
 // with an event; a solve / halo pack / unpack on a CALLER's stream orders itself behind it
 // (the device-plan upload returns with k_init_state still in flight).
@@ -684,7 +280,7 @@ int flame_hip_graph_resize(flame_hip_graph* g, int32_t V, int32_t E, int32_t T) 
     HIPCHK(hipSetDevice(g->device));
     HIPCHK(wait_last_solve(g));
     HIPCHK(hipStreamSynchronize(g->stream));
-    persist_discard(g);
+    g->res.discard(g);
   }
   g->V = V; g->E = E; g->T = T;
   g->uploaded = false;
@@ -695,6 +291,7 @@ int flame_hip_graph_resize(flame_hip_graph* g, int32_t V, int32_t E, int32_t T) 
 int flame_hip_set_option(flame_hip_graph* g, const char* key, int32_t value) {
   if (!g || !key) return FLAME_HIP_ERR_ARG;
   const std::string k(key);
+  int rc = 0;
   if (k == "path") {
     if (value < 0 || value > 2) return FLAME_HIP_ERR_ARG;
     g->opt.path = value;
@@ -737,21 +334,8 @@ int flame_hip_set_option(flame_hip_graph* g, const char* key, int32_t value) {
   } else if (k == "stream_depth") {
     if (value < 0 || value > kMaxDepth) return FLAME_HIP_ERR_ARG;
     g->stream_depth = value;
-  } else if (k == "persist") {
-    g->persist = value != 0;  // (2 was r03's "also size small frames for it": the automatic tiles do as well now)
-  } else if (k == "persist_prof") {
-    if (value < 0) return FLAME_HIP_ERR_ARG;
-    g->persist_prof_want = value;
-  } else if (k == "one_xcd") {
-    g->one_xcd_opt = value != 0;
-  } else if (k == "poll_delay") {  // x 256 clocks between a round's stores and its first poll pass; -1 = automatic
-    if (value < -1 || value > 255) return FLAME_HIP_ERR_ARG;
-    g->poll_delay_opt = value;
-  } else if (k == "persist_timeout_us") {  // what a poll may wait before the launch gives up; 0 = automatic
-    if (value < 0) return FLAME_HIP_ERR_ARG;
-    g->persist_timeout_opt = value;
-  } else if (k == "need_marks") {  // fat tiles hand over only what somebody polls (default 1)
-    g->need_marks = value != 0;
+  } else if (g->res.set_option(k, value, &rc)) {  // "persist", "persist_prof", "one_xcd", "poll_delay", "persist_timeout_us", "need_marks"
+    return rc;
   } else if (k == "plan_timing") {  // diagnostic: the plan builders' stages on stderr (levels: plan_dev.hip)
     if (value < 0 || value > 5) return FLAME_HIP_ERR_ARG;
     g->opt.timing = value;
@@ -770,6 +354,7 @@ int flame_hip_get_info(const flame_hip_graph* g, const char* key, int64_t* value
   if (!g || !key || !value) return FLAME_HIP_ERR_ARG;
   const std::string k(key);
   const Plan& P = g->plan;
+  int rc = 0;
   if (k == "V") *value = g->V;
   else if (k == "E") *value = g->E;
   else if (k == "T") *value = g->T;
@@ -792,45 +377,8 @@ int flame_hip_get_info(const flame_hip_graph* g, const char* key, int64_t* value
   else if (k == "tile_imbalance_pct") *value = P.on_device ? g->tile_imbalance_pct : 0;
   else if (k == "plan_mini") *value = (P.on_device && g->plan_mini_used) ? 1 : 0;
   else if (k == "stream_depth") *value = g->stream_depth;
-  else if (k == "persist") *value = g->persist ? 1 : 0;
-  else if (k == "persist_used") *value = g->persist_used ? 1 : 0;
-  else if (k == "one_xcd_used") *value = (g->persist_used && g->one_xcd_used) ? 1 : 0;
-  else if (k == "one_xcd") *value = g->one_xcd_opt ? 1 : 0;
-  else if (k == "persist_recovered") *value = g->persist_recovered;
-  else if (k == "persist_launches") *value = g->persist_launches;
-  else if (k == "persist_timeout_us") *value = g->persist_timeout_us;
-  else if (k == "persist_torn") {  // torn hand-off entries seen so far (only a FLAME_TORN_CHECK build counts; synchronise first)
-    int32_t v = 0;
-    if (g->xp.prof && hipMemcpy(&v, g->xp.prof + 8, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return FLAME_HIP_ERR_HIP;
-    *value = v;
-  }
   else if (k == "torn_check_build") *value = tile_torn_check_build() ? 1 : 0;
-  else if (k == "persist_round_ns") *value = (int64_t)(g->persist_round_us * 1e3f);
-  else if (k == "persist_wait_us_max") {  // the longest a poll of any wave waited since the last look (read and cleared; synchronise first)
-    int32_t v = 0;
-    if (!g->xp.prof) { *value = 0; return 0; }
-    if (hipMemcpy(&v, g->xp.prof + 7, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemset(g->xp.prof + 7, 0, sizeof(v)) != hipSuccess) return FLAME_HIP_ERR_HIP;
-    *value = v / 100;
-  }
-  else if (k == "persist_gave_up") *value = persist_gave_up_count(g->device);  // (give-ups of any handle on this device)
-  else if (k == "persist_backoff") *value = g->device >= 0 ? persist_backoff(g->device) : 0;  // solves the device's lease still sits out (plans uploaded meanwhile are sized for launches)
-  else if (k == "one_xcd_allowed") *value = one_xcd_allowed(g->device) ? 1 : 0;  // 0: a one-XCD launch gave up in this process, the mode is off
-  else if (k == "persist_gave_up_tile") *value = g->give_up.tile;        // (this handle's last give-up, see GiveUp)
-  else if (k == "persist_gave_up_round") *value = g->give_up.round;
-  else if (k == "persist_gave_up_front_round") *value = g->give_up.front_round;
-  else if (k == "persist_gave_up_not_started") *value = g->give_up.not_started;
-  else if (k == "persist_gave_up_rounds") *value = g->give_up.rounds;
-  else if (k == "persist_gave_up_tiles") *value = g->give_up.tiles;
-  else if (k == "persist_gave_up_one_xcd") *value = g->give_up.one_xcd;
-  else if (k == "persist_gave_up_timeout_us") *value = g->give_up.timeout_us;
-  else if (k.rfind("persist_prof_", 0) == 0) {  // dev aid (option "persist_prof" = <tile + 1>): 10 ns ticks of that tile, summed over rounds
-    const int i = std::atoi(k.c_str() + 13);
-    int32_t v = 0;
-    if (i < 0 || i > 4 || !g->xp.prof) return FLAME_HIP_ERR_ARG;
-    if (hipMemcpy(&v, g->xp.prof + 2 + i, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return FLAME_HIP_ERR_HIP;
-    *value = v;
-  }
+  else if (g->res.info(g, k, value, &rc)) return rc;  // "persist*", "one_xcd*": the resident solve's
   else if (k == "delaunay_hull") *value = g->dt.last_hull;  // flame_hip_delaunay: boundary vertices / live points / host microseconds of the last call
   else if (k == "delaunay_live") *value = g->dt.last_live;
   else if (k == "delaunay_us") *value = (int64_t)(g->dt.last_ms * 1000.0f);
@@ -897,11 +445,7 @@ struct GraphOptScope {
   int saved_single_max, saved_depth;
   GraphOptScope(flame_hip_graph* g_, int32_t V) : g(g_), saved_single_max(g_->opt.single_max), saved_depth(g_->opt.tile_depth) {
     g->opt.single_max = std::min(g->opt.single_max, g->single_cap);
-    // (plan-only handles size their tiles the same way: they are the device plans' reference.  ADVICE r4: the depth follows
-    // whether resident tiles can actually be taken -- not while the device's lease sits out a back-off after a give-up, not
-    // under the in-kernel timeline -- because depth 5 by ordinary launches is the slower configuration)
-    g->opt.resident = g->persist && !g->prof && (g->device < 0 || persist_backoff(g->device) == 0);
-    g->opt.one_xcd = g->opt.resident && g->one_xcd_opt && g->opt.num_cus >= 256 && one_xcd_allowed(g->device);
+    g->res.sizing(g, &g->opt.resident, &g->opt.one_xcd);  // (whether resident tiles can actually be taken)
     if (g->stream_depth > 0 && g->opt.tile_depth == 0 && g->opt.tile_own <= 0 && g->opt.batch_voff.empty() && V <= 64 * 32)
       g->opt.tile_depth = g->stream_depth;
   }
@@ -909,9 +453,6 @@ struct GraphOptScope {
   GraphOptScope(const GraphOptScope&) = delete;
   GraphOptScope& operator=(const GraphOptScope&) = delete;
 };
-
-// LDS the resident tiles' poll delivery needs behind a tile's incidence slots: the primal state of the halo vertices it updates
-static size_t persist_stage_bytes(const TileDesc& D) { return sizeof(float4) * (size_t)std::max(D.n_upd - D.n_own, 0); }
 
 static int upload_device_plan(flame_hip_graph* g, const float* pos, const int32_t* edges,
                               const float* alpha, const float* beta, const float* z, const float* wgt,
@@ -1065,13 +606,8 @@ static int upload_device_plan(flame_hip_graph* g, const float* pos, const int32_
       // can be resident on it.  One hull tile of THIS frame with a halo twice the others' (the old partition knows nothing
       // of its long edges) is enough for a configuration the resident kernels do not have, and the whole solve went by
       // launches (r05: every 4th frame of the 50 k stream, 2.8 ms instead of 1.3): such a frame is bisected anew.
-      if (ok && reusing && g->opt.resident && ntiles >= 2 && ntiles <= std::min(kPersistMaxTiles, g->num_cus)) {
-        size_t stage = 0;
-        for (const TileDesc& D : tiles) stage = std::max(stage, persist_stage_bytes(D));
-        if (!(slot12 ? tile_slot12_exists(cfg_nt, cfg_ept, cfg_vpt) : tile_persist_exists(cfg_nt, cfg_ept, cfg_vpt)) ||
-            (size_t)lds_max + stage + (size_t)kTileLdsReserve > (size_t)g->opt.lds_bytes)
-          ok = false;
-      }
+      if (ok && reusing && g->opt.resident && ntiles >= 2 && ntiles <= std::min(kPersistMaxTiles, g->num_cus))
+        ok = resident_fits(lds_max, (int64_t)ResidentSolve::stage_bytes(tiles), slot12, cfg_nt, cfg_ept, cfg_vpt, g->opt.lds_bytes);
     }
     if (reusing) {
       if (ok) { built = true; g->plan_reused = true; g->reuse_backoff = 0; break; }
@@ -1190,7 +726,7 @@ int flame_hip_graph_upload(flame_hip_graph* g, const float* pos, const int32_t* 
     HIPCHK(hipSetDevice(g->device));
     HIPCHK(wait_last_solve(g));
     HIPCHK(hipStreamSynchronize(g->stream));
-    persist_discard(g);
+    g->res.discard(g);
     HIPCHK(hipStreamSynchronize(g->stream_in));
     HIPCHK(g->planner.wait_maps());  // (the previous frame's maps read its positions / tiles on the builder's stream)
     g->drop_execs();  // captured launches hold the old grid / pointers
@@ -1323,11 +859,8 @@ int flame_hip_graph_upload(flame_hip_graph* g, const float* pos, const int32_t* 
 
 // buffers every uploaded graph needs, whichever builder made its plan
 static int finish_upload(flame_hip_graph* g) {
-  g->poll_valid = false;  // (new tile arrays: the resident tiles' poll lists are rebuilt at their next launch)
   const int32_t V = g->V, E = g->E;
-  // (the round time the resident launches' time-out follows was measured on ANOTHER graph -- a frame stream's
-  // next frame is about as large and keeps it, a graph of another size starts again from the 4 ms of a first launch)
-  if (g->persist_round_V > 0 && (V > 2 * g->persist_round_V || 2 * V < g->persist_round_V)) { g->persist_round_us = 0.f; g->persist_round_V = 0; }
+  g->res.plan_changed(V);
   const Plan& P = g->plan;
   int rc;
   if ((rc = dev_alloc(g->caps, &g->vtx_normals, (size_t)V))) return rc;
@@ -1397,7 +930,7 @@ int flame_hip_graph_sync(flame_hip_graph* g, const flame_hip_sync_params* sp, in
     HIPCHK(wait_last_solve(g));
     hipStream_t s = g->stream;
     HIPCHK(hipStreamSynchronize(s));
-    persist_discard(g);
+    g->res.discard(g);
     HIPCHK(g->planner.wait_maps());
     if ((rc = dev_alloc(g->caps, &g->in_pos, (size_t)V)) || (rc = dev_alloc(g->caps, &g->in_tris, 3 * (size_t)T)) ||
         (rc = dev_alloc(g->caps, &g->in_mu, (size_t)V)) || (rc = dev_alloc(g->caps, &g->in_var, (size_t)V)) ||
@@ -1655,7 +1188,7 @@ int flame_hip_graph_update_data(flame_hip_graph* g, const float* z, const float*
   HIPCHK(hipSetDevice(g->device));
   HIPCHK(wait_last_solve(g));
   HIPCHK(hipStreamSynchronize(g->stream));
-  if (g->persist_unchecked && (rc = flame_hip_sync(g))) return rc;  // (a resident launch that gave up is repeated first)
+  if (g->res.pending() && (rc = flame_hip_sync(g))) return rc;  // (a resident launch that gave up is repeated first)
   if ((rc = dev_alloc(g->caps, &g->in_z, (size_t)V)) || (rc = dev_alloc(g->caps, &g->in_wgt, (size_t)V)) ||
       (rc = dev_alloc(g->caps, &g->in_x0, (size_t)V)))
     return rc;
@@ -1686,7 +1219,7 @@ int flame_hip_set_state(flame_hip_graph* g, const float* x, const float* w1, con
   HIPCHK(hipSetDevice(g->device));
   HIPCHK(wait_last_solve(g));
   HIPCHK(hipStreamSynchronize(g->stream));
-  if (g->persist_unchecked && (rc = flame_hip_sync(g))) return rc;  // (a resident launch that gave up is repeated first)
+  if (g->res.pending() && (rc = flame_hip_sync(g))) return rc;  // (a resident launch that gave up is repeated first)
   if ((rc = ensure_host_perms(g))) return rc;
   g->state_serial++;
   if (x || w1 || w2 || xb || w1b || w2b) {
@@ -1717,327 +1250,20 @@ int flame_hip_set_state(flame_hip_graph* g, const float* x, const float* w1, con
   return 0;
 }
 
-// Enqueue the launches of `num_iters` PD iterations on stream s, starting from buffer `cur`.
-// Returns the buffer index holding the result through *cur_out.
-// one launch of resident tiles instead of ceil(num_iters / depth) launches?
-// one launch of resident tiles instead of ceil(num_iters / depth) launches?
-static bool persist_applies(const flame_hip_graph* g, int32_t num_iters) {
-  const Plan& P = g->plan;
-  if (!g->persist || g->persist_skip_once || g->path != FLAME_HIP_PATH_TILE || g->prof || P.tile_depth <= 0 ||
-      num_iters <= P.tile_depth)
-    return false;
-  const size_t nt = P.tiles.size();
-  if (nt < 2 || nt > (size_t)kPersistMaxTiles || (int)nt > g->num_cus) return false;  // (one workgroup per CU is always resident)
-  if (!(P.tile_slot12 ? tile_slot12_exists(P.tile_threads, P.tile_ept, P.tile_vpt)
-                      : tile_persist_exists(P.tile_threads, P.tile_ept, P.tile_vpt)))
-    return false;
-  size_t stage = 0;
-  for (const TileDesc& D : P.tiles) {
-    if (D.n_ext <= 0) return false;  // (an empty tile has nothing to hand over, but its neighbours would not know)
-    stage = std::max(stage, persist_stage_bytes(D));
-  }
-  // (r05: what a tile polls is delivered through an LDS staging area behind its incidence slots)
-  if ((size_t)P.tile_lds_bytes + stage + (size_t)kTileLdsReserve > (size_t)g->opt.lds_bytes) return false;
-  return true;
-}
-
-// Resident tiles need every workgroup of their launch on the chip at once.  Two such launches from two handles of one
-// process can each get part of the CUs and starve each other until both time out, so a device has ONE lease: a handle
-// takes it for a solve and holds it until that solve's end event has fired; a handle that finds it taken solves by
-// ordinary launches.  After a launch gave up for any other reason (a foreign kernel holding CUs, another process) the
-// whole process stays off resident tiles for a while: 16 solves, doubling up to 4096 with every further give-up.
-struct PersistLease {
-  std::mutex m;
-  flame_hip_graph* holder = nullptr;
-  hipEvent_t holder_done = nullptr;  // (the holder's ev1)
-  hipStream_t holder_stream = nullptr;  // the stream its launch went to: a launch queued BEHIND it on the same stream can
-                                     // never be co-resident with it (the partition mode's parts of one rank)
-  bool recorded = false;             // the holder's end event has been recorded behind its launch (until then: busy)
-  bool one_xcd_broken = false;       // a one-XCD launch gave up on this device: the mode is off for the rest of the process
-  int backoff = 0;                   // solves (of any handle) to sit out
-  int backoff_next = 16;
-  int gave_up = 0;                   // give-ups seen on this device (info "persist_gave_up")
-};
-static PersistLease& persist_lease(int device) {
-  static PersistLease leases[64];
-  return leases[(unsigned)device & 63];
-}
-// wait_for_holder: a FAT plan -- halo depth 1 or 2, sized for ONE resident launch -- that finds the lease taken
-// would otherwise run as one 256-workgroup launch per 1-2 iterations, several times slower than waiting for the other
-// handle's solve to end; so it waits for the holder's end event (host side, bounded by that solve) and takes the lease then
-static bool persist_lease_take(flame_hip_graph* g, hipStream_t s, bool wait_for_holder = false) {
-  PersistLease& L = persist_lease(g->device);
-  std::unique_lock<std::mutex> lk(L.m);
-  if (L.backoff > 0) { --L.backoff; return false; }
-  if (L.holder && L.holder != g && (!L.recorded || (L.holder_stream != s && hipEventQuery(L.holder_done) != hipSuccess))) {
-    if (!wait_for_holder || !L.recorded || !L.holder_done) return false;
-    hipEvent_t ev = L.holder_done;
-    lk.unlock();
-    const hipError_t e = hipEventSynchronize(ev);  // (the event belongs to a live handle of this process: handles outlive their solves)
-    lk.lock();
-    if (e != hipSuccess || (L.holder && L.holder != g && hipEventQuery(L.holder_done) != hipSuccess)) return false;
-  }
-  L.holder = g;
-  L.holder_done = g->ev1;
-  L.holder_stream = s;
-  L.recorded = false;  // (flame_hip_solve records ev1 behind the launch, then persist_lease_recorded())
-  return true;
-}
-static void persist_lease_recorded(flame_hip_graph* g) {
-  PersistLease& L = persist_lease(g->device);
-  std::lock_guard<std::mutex> lk(L.m);
-  if (L.holder == g) L.recorded = true;
-}
-static int persist_gave_up_count(int device) {
-  PersistLease& L = persist_lease(device);
-  std::lock_guard<std::mutex> lk(L.m);
-  return L.gave_up;
-}
-static int persist_backoff(int device) {
-  PersistLease& L = persist_lease(device);
-  std::lock_guard<std::mutex> lk(L.m);
-  return L.backoff;
-}
-static bool one_xcd_allowed(int device) {
-  if (device < 0) return true;  // (a host-only plan: sized as the MI355X would)
-  PersistLease& L = persist_lease(device);
-  std::lock_guard<std::mutex> lk(L.m);
-  return !L.one_xcd_broken;
-}
-static void persist_lease_drop(flame_hip_graph* g, bool gave_up) {
-  PersistLease& L = persist_lease(g->device);
-  std::lock_guard<std::mutex> lk(L.m);
-  if (L.holder == g) { L.holder = nullptr; L.holder_done = nullptr; L.holder_stream = nullptr; }
-  if (gave_up && g->one_xcd_used) L.one_xcd_broken = true;
-  if (gave_up) {
-    ++L.gave_up;
-    L.backoff = L.backoff_next;
-    L.backoff_next = std::min(L.backoff_next * 2, 4096);
-  }
-}
-
+// Enqueue `num_iters` PD iterations on stream s, starting from buffer `cur`: ONE launch of resident tiles where that
+// applies and the device's lease is free, else the launches.  Returns the buffer index holding the result through *cur_out.
 static int enqueue_iterations(flame_hip_graph* g, const SolveParams& sp, int32_t num_iters, hipStream_t s, int cur,
-                              int* cur_out, int* launches);
-
-// After a synchronisation: did a launch of resident tiles give up (a wait timed out: not all of its workgroups were
-// on the chip)?  Returns 0 when there was nothing, 1 when the solve was REPEATED by ordinary launches (enqueued, not
-// yet waited for: the caller synchronises again and redoes what it had queued behind the solve), an error code when it
-// cannot be.  The launch only reads its source buffers, so it can be repeated whenever nothing else wrote the state
-// since.  own_marks: state-writing steps the CALLER itself queued behind the solve and will redo (frame_results'
-// un-scaling); anything else that wrote the state since (a graph filter, new data terms) cannot be replayed here
-static int persist_check(flame_hip_graph* g, int own_marks = 0) {
-  const bool force_fail = TEST_HOOK(persist_fail, 0) != 0;  // (hooks library only: the recovery path)
-  if (force_fail && g->persist_used && g->persist_err) *g->persist_err = 3;
-  g->persist_unchecked = false;  // (every caller has synchronised the solve's stream)
-  const int unchecked = g->persist_unchecked_n;
-  g->persist_unchecked_n = 0;
-  if (!g->persist_err || *g->persist_err == 0) {
-    if (g->persist_used && g->last_rounds > 0 && unchecked == 1) {  // the round time the next launch's time-out follows
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, g->ev0, g->ev1) == hipSuccess && ms > 0.f) { g->persist_round_us = ms * 1e3f / (float)g->last_rounds; g->persist_round_V = g->V; }
-      else (void)hipGetLastError();
-    }
-    g->queued.clear(); g->qsnap_valid = false;
-    return 0;
-  }
-  persist_note_give_up(g);
-  *g->persist_err = 0;
-  persist_lease_drop(g, true);
-  // r05: a queue of solves is repeated as a whole from the state copied aside in front of its second member
-  if (g->queued.size() > 1) {
-    std::vector<flame_hip_graph::QueuedSolve> q;
-    q.swap(g->queued);
-    const bool ok = g->qsnap_valid && g->state_serial == g->queued_serial + (uint64_t)q.size() + (uint64_t)own_marks;
-    g->qsnap_valid = false;
-    g->persist_used = false;
-    if (!ok) { g->uploaded = false; return FLAME_HIP_ERR_STATE; }
-    hipStream_t s = g->last_stream ? g->last_stream : g->stream;
-    const int src = g->queued_src;
-    HIPCHK(hipMemcpyAsync(g->A[src], g->qsnapA, sizeof(float4) * (size_t)g->V, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(g->B[src], g->qsnapB, sizeof(float4) * (size_t)g->V, hipMemcpyDeviceToDevice, s));
-    if (g->E > 0) HIPCHK(hipMemcpyAsync(g->q[src], g->qsnapq, sizeof(float4) * (size_t)g->E, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipEventRecord(g->ev0, s));
-    int cur = src, total_launches = 0;
-    g->persist_skip_once = true;
-    for (const auto& e : q) {
-      int cur_out = cur, launches = 0;
-      const int rc = enqueue_iterations(g, e.sp, e.iters, s, cur, &cur_out, &launches);
-      if (rc) { g->persist_skip_once = false; return rc; }
-      cur = cur_out; total_launches += launches;
-    }
-    g->persist_skip_once = false;
-    g->cur = cur;
-    g->state_serial++;
-    g->last_launches = total_launches;
-    HIPCHK(hipEventRecord(g->ev1, s));
-    ++g->persist_recovered;
-    return 1;
-  }
-  g->queued.clear(); g->qsnap_valid = false;
-  // (several solves queued without a synchronisation in between: an earlier one may have been the one that gave up, and
-  // the later ones started from its unfinished result -- nothing to repeat from)
-  const bool can = g->persist_used && unchecked <= 1 && g->state_serial == g->solve_serial + (uint64_t)own_marks && g->last_iters > 0;
-  g->persist_used = false;
-  if (!can) {
-    g->uploaded = false;  // the state is that of an unfinished solve
-    return FLAME_HIP_ERR_STATE;
-  }
-  hipStream_t s = g->last_stream ? g->last_stream : g->stream;
-  int cur_out = 0, launches = 0;
-  HIPCHK(hipEventRecord(g->ev0, s));
-  g->persist_skip_once = true;
-  int rc = enqueue_iterations(g, g->last_sp, g->last_iters, s, g->last_src, &cur_out, &launches);
-  g->persist_skip_once = false;
-  if (rc) return rc;
-  g->cur = cur_out;
-  g->state_serial++;
-  g->last_launches = launches;
-  HIPCHK(hipEventRecord(g->ev1, s));
-  ++g->persist_recovered;
-  return 1;
-}
-
-static int enqueue_iterations(flame_hip_graph* g, const SolveParams& sp, int32_t num_iters,
-                              hipStream_t s, int cur, int* cur_out, int* launches) {
-  const Plan& P = g->plan;
-  *launches = 0;
-  g->persist_used = false;
+                              int* cur_out, int* launches) {
   if (g->path == FLAME_HIP_PATH_TILE) {
-    TileArgs a;
-    a.tiles = g->tiles; a.t_vmap = g->t_vmap; a.t_emap = g->t_emap; a.t_eij = g->t_eij;
-    a.t_ew = g->t_ew; a.t_srow = g->t_srow; a.p = sp; a.ntiles = (int32_t)P.tiles.size();
-    a.prof = g->prof;
-    a.slot12 = P.tile_slot12 ? 1 : 0;
-    a.fat = P.tile_fat ? 1 : 0;
-    if (persist_applies(g, num_iters) && persist_lease_take(g, s, P.tile_fat && P.tile_depth <= 2)) {
-      PersistBufs& x = g->xp;
-      int rc;
-      if (!g->persist_err) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&g->persist_err), 64, hipHostMallocDefault));
-        *g->persist_err = 0;
-      }
-      if (!x.prof || g->persist_prof_set != g->persist_prof_want) {  // dev aid: which tile (if any) splits its rounds' time
-        if ((rc = dev_alloc(g->caps, &x.prof, 16))) return rc;
-        int32_t w[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        int want = g->persist_prof_want;
-        if (want > 0) { w[0] = 1; w[1] = want - 1; }
-        HIPCHK(memcpy_sync(s, x.prof, w, sizeof(w), hipMemcpyHostToDevice));
-        g->persist_prof_set = g->persist_prof_want;
-      }
-      const int rounds = (num_iters + P.tile_depth - 1) / P.tile_depth;
-      bool rezero = g->persist_base > (1 << 23);  // (the tags only grow; 2^23: the torn-read debug build compares 24 bits)
-      if (rezero) g->persist_base = 0;
-      // the tiles' poll lists: in local order for the FIRST solve of a plan (a frame of a stream is solved once and would
-      // not earn the sorts back), address-sorted from the second solve on (a resident graph; the lane order, applied then,
-      // invalidates them anyway)
-      const bool want_sorted = g->solves_since_upload > 0;
-      if (!g->poll_valid || (want_sorted && !g->poll_sorted)) {
-        size_t nv_loc = 0, ne_loc = 0;
-        for (const TileDesc& D : P.tiles) { nv_loc += (size_t)D.n_ext; ne_loc += (size_t)D.e_loc; }
-        // (+ 1: a tile without local edges still reads the list's entry at its own offset -- the last tile's is one past the end)
-        if ((rc = dev_alloc(g->caps, &x.poll_v, nv_loc + 1)) || (rc = dev_alloc(g->caps, &x.poll_e, ne_loc + 1)) ||
-            (rc = dev_alloc(g->caps, &x.poll_ne, P.tiles.size())))
-          return rc;
-        // (r05: the sorted lists' kernel also marks what anybody polls; the rest of a tile's own entries is not handed over.
-        // A plan's first solve -- a frame of a stream -- stores everything and pays neither the marks nor their memsets)
-        x.need_valid = false;
-        if (want_sorted && g->need_marks && P.tile_fat) {  // (the FAT kernel variants read the marks)
-          if ((rc = dev_alloc(g->caps, &x.need_v, std::max<size_t>((size_t)g->V, 1))) || (rc = dev_alloc(g->caps, &x.need_e, std::max<size_t>((size_t)g->E, 1))))
-            return rc;
-          HIPCHK(hipMemsetAsync(x.need_v, 0, sizeof(int32_t) * std::max<size_t>((size_t)g->V, 1), s));
-          HIPCHK(hipMemsetAsync(x.need_e, 0, sizeof(int32_t) * std::max<size_t>((size_t)g->E, 1), s));
-          x.need_valid = true;
-        }
-        HIPCHK(launch_poll_lists(s, (int32_t)P.tiles.size(), g->tiles, g->t_vmap, g->t_emap, g->t_eij, x.poll_v, x.poll_e, x.poll_ne, want_sorted,
-                                 x.need_valid ? x.need_v : nullptr, x.need_valid ? x.need_e : nullptr));
-        g->poll_sorted = want_sorted;
-        x.stage_bytes = 0;
-        for (const TileDesc& D : P.tiles) x.stage_bytes = std::max(x.stage_bytes, persist_stage_bytes(D));
-        g->poll_valid = true;
-      }
-      for (int b = 0; b < 2; ++b) {  // (a new or recycled buffer is zeroed: tag 0 is never a round's)
-        float4** pp[3] = {&x.hA[b], &x.hB[b], &x.hq[b]};
-        const size_t nn[3] = {(size_t)g->V, (size_t)g->V, (size_t)std::max(g->E, 1)};
-        for (int k = 0; k < 3; ++k) {
-          bool fresh = false;
-          if ((rc = dev_alloc_uncached(g->device, pp[k], &g->xp_cap[3 * b + k], nn[k], &fresh))) return rc;
-          if (fresh || rezero) HIPCHK(hipMemsetAsync(*pp[k], 0, g->xp_cap[3 * b + k], s));
-        }
-      }
-      PersistBufs xl = x;  // (what this launch gets)
-      g->one_xcd_used = false;
-      if (g->one_xcd_opt && P.tiles.size() <= (size_t)kOneXcdTiles && g->num_cus >= 256 && one_xcd_allowed(g->device)) {
-        for (int b = 0; b < 2; ++b) {
-          float4** pp[3] = {&g->cA[b], &g->cB[b], &g->cq[b]};
-          const size_t nn[3] = {(size_t)g->V, (size_t)g->V, (size_t)std::max(g->E, 1)};
-          for (int k = 0; k < 3; ++k) {
-            if ((rc = dev_alloc(g->caps, pp[k], nn[k]))) return rc;
-            const size_t cap_now = g->caps[(void*)pp[k]];
-            if (g->c_zeroed[3 * b + k] != (void*)*pp[k] || g->c_zeroed_cap[3 * b + k] != cap_now || rezero) {  // (a new or re-grown
-              HIPCHK(hipMemsetAsync(*pp[k], 0, cap_now, s));                                                   // allocation: garbage could pass for a tag)
-              g->c_zeroed[3 * b + k] = (void*)*pp[k];
-              g->c_zeroed_cap[3 * b + k] = cap_now;
-            }
-          }
-          xl.hA[b] = g->cA[b]; xl.hB[b] = g->cB[b]; xl.hq[b] = g->cq[b];
-        }
-        xl.one_xcd = 1;
-        g->one_xcd_used = true;
-      }
-      a.A_src = g->A[cur]; a.B_src = g->B[cur]; a.q_src = g->q[cur];
-      a.A_dst = g->A[cur ^ 1]; a.B_dst = g->B[cur ^ 1]; a.q_dst = g->q[cur ^ 1];
-      a.iters = num_iters;
-      {
-        // (the lists in local order: a pass is long enough, 0; fat tiles with a 1- or 2-iteration round: the hand-off is the
-        // larger part of the round and the first pass should not wait -- 200 k 3.02 / 3.05 / 3.13 / 3.15 / 3.23 us per
-        // iteration at 0 .. 4, 160 k and 100 k (depth 3) flat: profiles/r05_fat_poll_delay.txt)
-        const bool short_fat_round = g->V > 256 * 196 && P.tile_depth <= 2;
-        x.poll_delay = g->poll_delay_opt >= 0 ? g->poll_delay_opt : ((g->poll_sorted && !short_fat_round) ? kPollDelayDefault : 0);
-        // A poll waits at most max(0.5 ms, 8 x the handle's last measured round) -- r04's flat 4 ms was 5.5 headline
-        // solves; 4 ms while nothing has been measured.  Option "persist_timeout_us" overrides.
-        const float us = g->persist_timeout_opt > 0 ? (float)g->persist_timeout_opt : (g->persist_round_us > 0.f ? std::max(500.f, 8.f * g->persist_round_us) : 4000.f);
-        g->persist_timeout_us = (int32_t)std::min(us, 1.0e6f);
-        x.timeout_ticks = g->persist_timeout_us * 100;
-        const int stall_us = TEST_HOOK(persist_stall_us, 0);  // (hooks library: a REAL late tile, tests/test_gpu_persist.py)
-        if (stall_us > 0 && tile_stall_hook_build()) x.poll_delay = (x.poll_delay & 0xff) | (stall_us << 8);  // (microseconds, bits 8.. of poll_delay; debug kernels only)
-      }
-      g->last_rounds = rounds;
-      // (one XCD: a pass through the L2 is short and cheap -- no pause in front of the first one, profiles/r06_one_xcd_ab.txt)
-      xl.poll_delay = (xl.one_xcd && g->poll_delay_opt < 0) ? 0 : x.poll_delay;
-      xl.timeout_ticks = x.timeout_ticks;
-      HIPCHK(launch_tile_persist(s, P.tile_threads, P.tile_ept, P.tile_vpt, (size_t)P.tile_lds_bytes, a, xl, g->persist_err,
-                                 g->persist_base));
-      g->give_up_base = g->persist_base;
-      g->persist_base += rounds - 1;
-      g->persist_used = true;
-      g->persist_unchecked = true;
-      ++g->persist_unchecked_n;
-      ++g->persist_launches;
-      g->last_src = cur;
+    bool taken = false;
+    if (int rc = g->res.launch(g, sp, num_iters, s, cur, &taken)) return rc;
+    if (taken) {
       *launches = 1;
-      *cur_out = cur ^ 1;  // (written once, by the last round; the source buffers are only read)
+      *cur_out = cur ^ 1;
       return 0;
     }
-    const int per = P.tile_depth > 0 ? P.tile_depth : num_iters;
-    for (int32_t done = 0; done < num_iters;) {
-      const int32_t n = std::min<int32_t>(per, num_iters - done);
-      a.A_src = g->A[cur]; a.B_src = g->B[cur]; a.q_src = g->q[cur];
-      a.A_dst = g->A[cur ^ 1]; a.B_dst = g->B[cur ^ 1]; a.q_dst = g->q[cur ^ 1];
-      a.iters = n;
-      HIPCHK(launch_tile(s, P.tile_threads, P.tile_ept, P.tile_vpt, (size_t)P.tile_lds_bytes, a));
-      cur ^= 1;
-      done += n;
-      ++*launches;
-    }
-  } else {
-    for (int32_t it = 0; it < num_iters; ++it) {
-      HIPCHK(launch_dual(s, g->E, g->eij, g->ew, g->B[cur], g->q[cur], sp.sigma));
-      HIPCHK(launch_primal(s, g->V, g->grow, g->ginc, g->ew, g->q[cur], g->A[cur], g->B[cur], sp));
-      *launches += 2;
-    }
   }
-  *cur_out = cur;
-  return 0;
+  return enqueue_by_launches(g, sp, num_iters, s, cur, cur_out, launches);
 }
 
 int flame_hip_solve(flame_hip_graph* g, const flame_hip_params* p, int32_t num_iters,
@@ -2066,31 +1292,16 @@ int flame_hip_solve(flame_hip_graph* g, const flame_hip_params* p, int32_t num_i
     if (g->timed) HIPCHK(hipStreamWaitEvent(s, g->ev1, 0));  // (the first solve may have run on another stream)
     HIPCHK(launch_assign_lanes(s, (int32_t)g->plan.tiles.size(), e_max, g->tiles, g->t_eij, g->t_ew, g->t_emap, g->plan.tile_slot12));
     g->lanes_applied = true;
-    g->poll_valid = false;  // (edges moved inside their 64-blocks: a poll record names a position)
+    g->res.lanes_changed();
   }
-  // r05: a solve queued behind an unchecked resident one -- before it overwrites that one's source, the source is set aside
-  if (g->persist_unchecked_n == 0) { g->queued.clear(); g->qsnap_valid = false; }
-  if (g->queued.size() == 1 && !g->qsnap_valid && g->state_serial == g->queued_serial + 1 && num_iters > 0) {
-    int rc2;
-    if ((rc2 = dev_alloc(g->caps, &g->qsnapA, (size_t)g->V)) || (rc2 = dev_alloc(g->caps, &g->qsnapB, (size_t)g->V)) ||
-        (rc2 = dev_alloc(g->caps, &g->qsnapq, (size_t)std::max(g->E, 1))))
-      return rc2;
-    const int src = g->queued_src;
-    HIPCHK(hipMemcpyAsync(g->qsnapA, g->A[src], sizeof(float4) * (size_t)g->V, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(g->qsnapB, g->B[src], sizeof(float4) * (size_t)g->V, hipMemcpyDeviceToDevice, s));
-    if (g->E > 0) HIPCHK(hipMemcpyAsync(g->qsnapq, g->q[src], sizeof(float4) * (size_t)g->E, hipMemcpyDeviceToDevice, s));
-    g->qsnap_valid = true;
-  }
+  if ((rc = g->res.before_solve(g, s, sp, num_iters))) return rc;
   const int cur_before = g->cur;
   const uint64_t serial_before = g->state_serial;
   HIPCHK(hipEventRecord(g->ev0, s));
-  g->last_sp = sp; g->last_iters = num_iters; g->last_stream = s;
-  // (a hipGraph replay or a solve of 0 iterations does not pass through enqueue_iterations(); without this a
-  // stale `persist_used` made persist_check() repeat the SHORT solve from buffers the replay had already overwritten)
-  g->persist_used = false;
+  g->last_stream = s;
   int launches = 0, cur_out = g->cur;
   if (num_iters > 0 && g->V > 0) {
-    if (g->use_graph && g->solves_since_upload > 0 && !persist_applies(g, num_iters)) {  // a frame stream that re-uploads before
+    if (g->use_graph && g->solves_since_upload > 0 && !g->res.applies(g, num_iters)) {  // a frame stream that re-uploads before
       // every solve never pays capture + instantiate; the captured launches replay on any stream
       // (the subdomain solver of the multi-GPU path passes its own)
       GraphExecEntry* hit = nullptr;
@@ -2125,24 +1336,15 @@ int flame_hip_solve(flame_hip_graph* g, const flame_hip_params* p, int32_t num_i
   }
   g->cur = cur_out;
   g->state_serial++;
-  g->solve_serial = g->state_serial;
-  if (num_iters > 0 && g->V > 0) {  // (the log of what a give-up would have to repeat)
-    if (g->queued.empty()) {
-      if (g->persist_used) { g->queued.push_back({sp, num_iters}); g->queued_src = cur_before; g->queued_serial = serial_before; }
-    } else if (g->qsnap_valid) {
-      g->queued.push_back({sp, num_iters});
-    } else {
-      g->queued.push_back({sp, num_iters});  // (no copy was taken -- something else wrote the state in between: the check refuses)
-    }
-  }
+  g->res.after_solve(g, sp, num_iters, cur_before, serial_before);
   g->last_launches = launches;
   g->solves_since_upload++;
   HIPCHK(hipEventRecord(g->ev1, s));
-  if (g->persist_used) persist_lease_recorded(g);
+  g->res.end_recorded(g);
   g->timed = true;
   // the maps of the NEXT frame's builder: enqueued behind this frame's iterations -- and, when those run as ONE launch of
   // resident tiles, ordered behind it too (they then overlap the results stage instead of fighting the tiles for CUs)
-  HIPCHK(g->planner.flush_grid(g->persist_used ? g->ev1 : nullptr));
+  HIPCHK(g->planner.flush_grid(g->res.used() ? g->ev1 : nullptr));
   return 0;
 }
 
@@ -2152,7 +1354,7 @@ int flame_hip_sync(flame_hip_graph* g) {
   HIPCHK(hipSetDevice(g->device));
   if (g->timed) HIPCHK(hipEventSynchronize(g->ev1));
   HIPCHK(hipStreamSynchronize(g->stream));
-  rc = persist_check(g);
+  rc = g->res.check(g);
   if (rc == 1) {  // the solve was repeated by launches: wait for those
     HIPCHK(hipEventSynchronize(g->ev1));
     HIPCHK(hipStreamSynchronize(g->stream));
@@ -2408,7 +1610,7 @@ int flame_hip_frame_results(flame_hip_graph* g, const flame_hip_params* p, float
     }
   }
   HIPCHK(hipStreamSynchronize(s));
-  if ((rc = persist_check(g, scale_back != 1.0f ? 1 : 0)) != 0) {
+  if ((rc = g->res.check(g, scale_back != 1.0f ? 1 : 0)) != 0) {
     if (rc != 1) return rc;
     // the solve was repeated by launches (its state is the initial one again, un-scaled): the whole call once more
     g->state_scale = 1.0f;
@@ -2447,7 +1649,7 @@ int flame_hip_debug_image(flame_hip_graph* g, int32_t kind, const float Kinv[9],
   HIPCHK(hipSetDevice(g->device));
   // (a launch of resident tiles that gave up is noticed -- and repeated -- at a synchronising call: an image must not
   // be drawn from an unfinished solve)
-  if (g->persist_unchecked && (rc = flame_hip_sync(g))) return rc;
+  if (g->res.pending() && (rc = flame_hip_sync(g))) return rc;
   hipStream_t s = g->stream;
   if (g->timed) HIPCHK(hipStreamWaitEvent(s, g->ev1, 0));
   if ((rc = ensure_raster(g, Kinv, tp, 1, 0.f, 0.f, false, false))) return rc;
@@ -2516,7 +1718,7 @@ int flame_hip_graph_filter(flame_hip_graph* g, int32_t kind, int32_t passes) {
   if (rc) return rc;
   if ((kind != 0 && kind != 1) || passes < 0) return FLAME_HIP_ERR_ARG;
   HIPCHK(hipSetDevice(g->device));
-  if (g->persist_unchecked && passes > 0 && (rc = flame_hip_sync(g))) return rc;  // (the filter rewrites what a repeat would need)
+  if (g->res.pending() && passes > 0 && (rc = flame_hip_sync(g))) return rc;  // (the filter rewrites what a repeat would need)
   if ((rc = dev_alloc(g->caps, &g->filter_tmp, (size_t)g->V))) return rc;
   if (g->timed) HIPCHK(hipStreamWaitEvent(g->stream, g->ev1, 0));
   for (int32_t k = 0; k < passes; ++k)
@@ -2531,7 +1733,7 @@ int flame_hip_scale_state(flame_hip_graph* g, float s) {
   if (rc) return rc;
   if (!std::isfinite(s)) return FLAME_HIP_ERR_NAN;
   HIPCHK(hipSetDevice(g->device));
-  if (g->persist_unchecked && (rc = flame_hip_sync(g))) return rc;
+  if (g->res.pending() && (rc = flame_hip_sync(g))) return rc;
   if (g->timed) HIPCHK(hipStreamWaitEvent(g->stream, g->ev1, 0));
   HIPCHK(launch_scale_state(g->stream, g->V, g->A[g->cur], g->B[g->cur], s));
   g->state_scale *= s;
@@ -2946,9 +2148,7 @@ int flame_hip_state_snapshot(flame_hip_graph* g, void* stream) {
     return rc;
   HIPCHK(order_after_state(g, s));
   if (g->timed && g->last_stream && g->last_stream != s) HIPCHK(hipStreamWaitEvent(s, g->ev1, 0));
-  HIPCHK(hipMemcpyAsync(g->snapA, g->A[g->cur], sizeof(float4) * V, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(g->snapB, g->B[g->cur], sizeof(float4) * V, hipMemcpyDeviceToDevice, s));
-  if (g->E > 0) HIPCHK(hipMemcpyAsync(g->snapq, g->q[g->cur], sizeof(float4) * (size_t)g->E, hipMemcpyDeviceToDevice, s));
+  if ((rc = copy_state(s, {g->snapA, g->snapB, g->snapq}, {g->A[g->cur], g->B[g->cur], g->q[g->cur]}, g->V, g->E))) return rc;
   g->snap_valid = true;
   g->snap_V = g->V; g->snap_E = g->E;
   return 0;
@@ -2962,10 +2162,7 @@ int flame_hip_state_rollback(flame_hip_graph* g, void* stream) {
   hipStream_t s = stream ? (hipStream_t)stream : g->stream;
   HIPCHK(order_after_state(g, s));
   if (g->timed && g->last_stream && g->last_stream != s) HIPCHK(hipStreamWaitEvent(s, g->ev1, 0));
-  const size_t V = (size_t)g->V;
-  HIPCHK(hipMemcpyAsync(g->A[g->cur], g->snapA, sizeof(float4) * V, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipMemcpyAsync(g->B[g->cur], g->snapB, sizeof(float4) * V, hipMemcpyDeviceToDevice, s));
-  if (g->E > 0) HIPCHK(hipMemcpyAsync(g->q[g->cur], g->snapq, sizeof(float4) * (size_t)g->E, hipMemcpyDeviceToDevice, s));
+  if ((rc = copy_state(s, {g->A[g->cur], g->B[g->cur], g->q[g->cur]}, {g->snapA, g->snapB, g->snapq}, g->V, g->E))) return rc;
   g->state_serial++;
   g->uploaded = true;  // (a give-up the handle could not repeat had marked the state unfinished)
   return 0;
@@ -2978,19 +2175,7 @@ int flame_hip_persist_take_error(flame_hip_graph* g, int32_t* gave_up) {
   int rc = require_device(g);
   if (rc) return rc;
   if (!gave_up) return FLAME_HIP_ERR_ARG;
-  const bool force_fail = TEST_HOOK(persist_fail, 0) != 0;  // (hooks library only: the recovery path)
-  *gave_up = 0;
-  const bool had = g->persist_unchecked;
-  g->persist_unchecked = false;
-  g->persist_unchecked_n = 0;
-  g->queued.clear(); g->qsnap_valid = false;  // (the caller -- the partition mode -- keeps snapshots of its own)
-  if (had && g->persist_err && (*g->persist_err != 0 || force_fail)) {
-    persist_note_give_up(g);
-    *g->persist_err = 0;
-    persist_lease_drop(g, true);
-    g->persist_used = false;
-    *gave_up = 1;
-  }
+  g->res.take_error(g, gave_up);
   return 0;
 }
 

@@ -233,7 +233,7 @@ struct InboxLayout {
   std::vector<size_t> rbuf_off[2];  // per local part, per parity: byte offset of its record buffer
   size_t bytes = 0;
 };
-// Freed uncached blocks are never handed back to the runtime (flame_hip.cpp UncachedPool: a later ordinary hipMalloc that
+// Freed uncached blocks are never handed back to the runtime (resident.cpp UncachedPool: a later ordinary hipMalloc that
 // recycles one misbehaves on ROCm 7.2): inboxes wait here for the next partition of the process.
 struct InboxPool {
   std::mutex m;

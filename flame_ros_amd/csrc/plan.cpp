@@ -307,6 +307,11 @@ bool PlanAttempts::regular_next() {
   return false;
 }
 
+bool resident_fits(int64_t lds_bytes, int64_t stage_bytes, bool slot12, int nt, int ept, int vpt, int64_t lds_avail) {
+  return (slot12 ? tile_slot12_exists(nt, ept, vpt) : tile_persist_exists(nt, ept, vpt)) &&
+         lds_bytes + stage_bytes + kTileLdsReserve <= lds_avail;
+}
+
 TileFit tile_fit(const PlanOptions& opt, bool fat, const std::vector<TileDesc>& tiles, bool allow_slot12) {
   TileFit f;
   int e_max = 0, ext_max = 0, upd_max = 0, hv_max = 0;
@@ -318,7 +323,7 @@ TileFit tile_fit(const PlanOptions& opt, bool fat, const std::vector<TileDesc>& 
     hv_max = std::max(hv_max, D.n_ext - D.n_own);
     lds16 = std::max(lds16, tile_lds_bytes(D.n_ext, D.nslots, false));
     lds12 = std::max(lds12, tile_lds_bytes(D.n_ext, D.nslots, true));
-    stage = std::max<int64_t>(stage, 16 * (int64_t)std::max(D.n_upd - D.n_own, 0));
+    stage = std::max(stage, persist_stage_bytes(D));
   }
   TileCfg c{};
   if (!fat) {
@@ -326,7 +331,7 @@ TileFit tile_fit(const PlanOptions& opt, bool fat, const std::vector<TileDesc>& 
     // (r06 / ADVICE r05: tiles that are meant to be resident must fit the way the resident launch needs them -- with its
     // staging area, in a configuration that has a resident kernel -- or the policy tries a shallower halo: PlanAttempts::regular_next())
     if (f.ok && wants_resident(opt, tiles.size()) && opt.tile_own <= 0 && opt.tile_depth <= 0 && opt.batch_voff.empty() && tiles[0].depth > 0 &&
-        (lds16 + stage + kTileLdsReserve > opt.lds_bytes || !tile_persist_exists(c.nt, c.ept, c.vpt)))
+        !resident_fits(lds16, stage, false, c.nt, c.ept, c.vpt, opt.lds_bytes))
       f.ok = false;
     f.lds_bytes = lds16;
   } else {

@@ -135,6 +135,12 @@ struct TileFit {
 // e_max / ext_max / upd_max / hv_max: the largest tile's local edges, local vertices, updated vertices, halo vertices;
 // lds16 / lds12: max over the tiles of tile_lds_bytes() (+ the resident tiles' staging area when `resident`)
 TileFit tile_fit(const PlanOptions& opt, bool fat, const std::vector<TileDesc>& tiles, bool allow_slot12 = true);
+// Can tiles of this configuration be RESIDENT (one launch for a whole solve)?  A resident kernel exists for it, and the
+// incidence slots (lds_bytes), the hand-off staging area behind them (stage_bytes) and the kernels' static LDS fit into
+// lds_avail.  (Fat tiles are priced by tile_fit() with margins of their own.)
+bool resident_fits(int64_t lds_bytes, int64_t stage_bytes, bool slot12, int nt, int ept, int vpt, int64_t lds_avail);
+// ... a tile's share of that staging area: the primal state (16 B) of the halo vertices it updates, which its polls deliver
+inline int64_t persist_stage_bytes(const TileDesc& D) { return 16 * (int64_t)(D.n_upd > D.n_own ? D.n_upd - D.n_own : 0); }
 // The attempt policy of BOTH plan builders (build_plan() on the host; flame_hip.cpp upload_device_plan() driving plan_dev.hip on
 // the device): which partition to build next.  A builder builds one attempt from tile_own() / depth(), prices it with
 // tile_fit(opt, fat(), tiles, fat_s12()) and does what after() returns; the body of each action is the builder's own.

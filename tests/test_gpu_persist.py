@@ -428,6 +428,40 @@ print("queue ok")
     assert out.returncode == 0 and "queue ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
 
 
+def test_a_give_up_that_an_upload_discards_only_costs_the_back_off(gpu):
+    """A resident solve gives up (the hooks library's forced error word) and the next upload arrives before anyone has
+    synchronised: nothing is repeated -- the upload throws that solve's state away -- but the give-up is counted and the
+    device's lease sits out its back-off; the solves of the new upload, by launches meanwhile, have the oracle's bits."""
+    import os, subprocess, sys
+    code = r'''
+import numpy as np, sys
+sys.path.insert(0, %r)
+from flame_ros_amd import graphgen
+from flame_ros_amd.regularizer import GraphRegularizer, default_params
+from oracle import COracle
+from oracle.cbind import default_params as oparams
+g, _ = graphgen.named("v800")
+p = default_params()
+r = GraphRegularizer(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, tris=g.tris, device=0, tile_own=30, tile_depth=8)
+assert r.info("num_tiles") >= 2
+r.step(p, 40, sync=False)
+assert r.info("persist_used") == 1 and r.info("persist_gave_up") == 0
+r.reupload(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt, tris=g.tris)   # (no synchronising call since the solve)
+assert r.info("persist_gave_up") == 1 and r.info("persist_recovered") == 0
+assert r.info("persist_backoff") > 0
+assert _hl.load().flame_hip_test_hook(b"persist_fail", 0) == 0   # (the hook off again: what follows are honest solves)
+o = COracle(g.pos, g.edges, g.alpha, g.beta, g.z, g.wgt); o.solve(oparams(), 40)
+r.step(p, 40, sync=False)
+x = r.download()[0]
+assert r.info("persist_gave_up") == 1 and r.info("persist_recovered") == 0
+assert np.array_equal(x.view(np.uint32), o.x.view(np.uint32))
+r.close()
+print("discard ok")
+''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", with_hooks(code, persist_fail=1)], env=hooks_env(), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "discard ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+
+
 @pytest.mark.parametrize("stall_us,gives_up", [(100, 0), (3000, 1)])
 def test_a_really_late_tile(gpu, stall_us, gives_up):
     """The time-out path with a REAL late tile, not a forced error word (test hook persist_stall_us: tile 0 sleeps in front
